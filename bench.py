@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- IQ Msamples/s through the RX hot path (sync + LS estimate + CP strip + FFT + equalise + de-map)
-on MI355X, with the kernel's HBM roofline fraction and a same-box CPU baseline.
+on MI355X, with the kernel's HBM roofline fraction (from events recorded inside the timed steps).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfgA|n128|n256|n512|n1024|n4096] [--lead random]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs if --dump-outputs is given and prints the line.
+`--full` adds everything else the line can carry: same-run copy / access-pattern / power probes, a same-box CPU baseline, the
+bit-error check of frame 0 and, at N > 1, the re-assembly check, an all-gather on its own and the counts-only step.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes THIS process a launcher: before anything touches the
 GPU it starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a child and
@@ -134,6 +139,25 @@ def rayleigh_taps(n_frames, seed):
     p = np.exp(-np.arange(8) / 2.0)
     t = (rng.standard_normal((n_frames, 8)) + 1j * rng.standard_normal((n_frames, 8))) * np.sqrt(p / 2)
     return (t / np.linalg.norm(t, axis=1, keepdims=True)).astype(np.complex64)
+
+
+DUMP_BYTES = 60 << 20          # --dump-outputs writes at most this much (the limit is 64 MB)
+
+
+def dump_outputs(torch, out_dir, eq, bits):
+    """--dump-outputs: what the last timed step returned, as float32 .npy files in `out_dir`.  `eq` [frames, data symbols, Kd, 2]
+    float32 (None with --no-eq) and `bits` [rows, bytes] uint8 (packed hard bits; at N > 1 the whole re-assembled stream) are far
+    larger than the budget at the bench sizes (7.5 GB and 0.5 GB at cfg2), so a fixed, seeded choice of whole frames / rows is
+    written, the budget split between them, beside the indices it took (`<name>_index.npy`, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(2026)
+    parts = [(name, t) for name, t in (("eq_symbols", eq), ("bits", bits)) if t is not None]
+    for name, t in parts:
+        n = int(t.shape[0])
+        k = max(1, min(n, DUMP_BYTES // len(parts) // (t[0].numel() * 4)))
+        idx = np.sort(rng.choice(n, k, replace=False))
+        np.save(os.path.join(out_dir, name + ".npy"), t[torch.from_numpy(idx).to(t.device)].to(torch.float32).cpu().numpy())
+        np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
 
 
 def _clean_env():
@@ -317,8 +341,13 @@ def main(argv=None):
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU and batch (default: the config's)")
     ap.add_argument("--no-eq", action="store_true", help="do not write equalised symbols (bits only)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-probes", action="store_true", help="skip the copy / access-pattern / power context probes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the context probes, the CPU baseline, the bit-error check and (N > 1) the "
+                         "re-assembly check, an all-gather alone and the counts-only step; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed, seeded sample of the last timed step's outputs (equalised symbols, packed bits) as DIR/*.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: skip the copy / access-pattern / power context probes")
     ap.add_argument("--chunks", type=int, default=4, help="sub-batches per step for all-gather overlap (N>1)")
     ap.add_argument("--mod", default=None, choices=sorted(BPS), help="override the config's constellation (numerology sweep)")
     ap.add_argument("--lead", default="aligned",
@@ -337,6 +366,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -524,11 +555,15 @@ def main(argv=None):
     step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])      # rank 0's launch stream
     value = samples_per_step / (elapsed / args.steps) / 1e6
 
+    d_bits, gathered = pipe.last()            # what the last step produced
+    if args.dump_outputs and rank == 0:
+        whole = d_bits if gathered is None else od.reassemble(torch, gathered, world).flatten(0, 1)
+        dump_outputs(torch, args.dump_outputs, d_eq, whole)
+
     # ---- correctness spot check of what was timed (rank 0): bit errors of frame 0 vs the transmitted bits
     ber = None
     gather_info = None
-    d_bits, gathered = pipe.last()            # what the last step produced
-    if rank == 0:
+    if rank == 0 and args.full:
         lead0 = 0 if inputs[0][2] is None else int(inputs[0][2][0])
         rxb = d_bits[0].cpu().numpy()
         txb = inputs[0][1][0].cpu().numpy()
@@ -538,6 +573,13 @@ def main(argv=None):
             keep = (len(rxb) // (n_sym // 4)) * ((fl - lead0) // (4 * L))
             ber = float(np.unpackbits(rxb[:keep] ^ txb[:keep]).sum()) / max(keep * 8, 1)
     if multi:
+        gather_info = dict(world_size=dist.get_world_size(), backend=dist.get_backend(), algorithm=pipe.algo, calibration=gather_calibration,
+                           rccl_version=_rccl_version(torch) if not rehearsal else None,
+                           bytes_contributed_per_rank_and_step=int(d_bits.numel()), bytes_received_per_rank_and_step=int(d_bits.numel() * (world - 1)),
+                           allgather_alone_ms=None, allgather_alone_busbw_GBs=None,
+                           allgather_in_loop_GBs_received_per_rank=round(d_bits.numel() * (world - 1) / (ms_per_step * 1e-3) / 1e9, 2),
+                           counts_only=None)
+    if multi and args.full:
         assert torch.equal(od.reassemble(torch, gathered, world)[rank].cpu(), d_bits.cpu()), "all-gather did not reassemble this rank's own shard"
         # one all-gather of a sub-batch on its own (untimed extra): what the fabric gives without demod traffic beside it
         f0, f1 = bounds[0]
@@ -588,11 +630,7 @@ def main(argv=None):
                                bit_errors_all_ranks=int(tot.item()), bits_all_ranks=int(d_bits.numel()) * 8 * world)
         except Exception as e:                      # never lose the measured line to the extra leg
             counts_only = dict(error="%s: %s" % (type(e).__name__, e))
-        gather_info = dict(world_size=dist.get_world_size(), backend=dist.get_backend(), algorithm=pipe.algo, calibration=gather_calibration,
-                           rccl_version=_rccl_version(torch) if not rehearsal else None,
-                           bytes_contributed_per_rank_and_step=int(d_bits.numel()), bytes_received_per_rank_and_step=int(d_bits.numel() * (world - 1)),
-                           allgather_alone_ms=round(g_ms, 4), allgather_alone_busbw_GBs=round(nb * (world - 1) / (g_ms * 1e-3) / 1e9, 2),
-                           allgather_in_loop_GBs_received_per_rank=round(d_bits.numel() * (world - 1) / (ms_per_step * 1e-3) / 1e9, 2),
+        gather_info.update(allgather_alone_ms=round(g_ms, 4), allgather_alone_busbw_GBs=round(nb * (world - 1) / (g_ms * 1e-3) / 1e9, 2),
                            counts_only=counts_only)
 
     out = None
@@ -618,7 +656,7 @@ def main(argv=None):
                 traffic_src = "profiles/%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel source, sha %s, kernel %s)" % (tf, sha, ent.get("kernel"))
                 break
         copy_gbs = pat_gbs = power = None
-        if world == 1 and not args.no_probes:
+        if world == 1 and args.full and not args.no_probes:
             # same-run context: this chip's float4 device-copy rate and the demod access pattern without arithmetic
             from ofdm_mi355x import _lib as ol
             d_rx0 = inputs[0][0]
@@ -698,7 +736,7 @@ def main(argv=None):
             contention["copy_GBs_if_alone"] = round(2 * nbytes * 10 / e0.elapsed_time(e1) / 1e6, 1)
             del src, dst
         cpu = None
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             cpu = cpu_baseline(cfg, inputs[0][0], fl)
         out = {
             "metric": METRIC,

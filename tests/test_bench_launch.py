@@ -50,6 +50,11 @@ def test_world_size_disagreement_fails_loudly():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_steps_must_be_positive():
+    r = _run("--steps", "0", "--dry-launch")
+    assert r.returncode != 0 and "--steps must be >= 1" in (r.stderr + r.stdout)
+
+
 def test_too_few_gpus_fails_before_any_rank_starts():
     import torch
     if torch.cuda.device_count() >= 2:

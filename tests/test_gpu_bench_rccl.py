@@ -21,7 +21,7 @@ def test_one_rank_rccl_group_runs_the_multi_gpu_path(extra):
     env = dict(os.environ, BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "128", "--steps", "3", "--warmup", "1", "--no-cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "128", "--steps", "3", "--warmup", "1", "--full", "--no-cpu",
                         "--no-probes"] + extra, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

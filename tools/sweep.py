@@ -8,7 +8,7 @@ out_json = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else N
 rows, lines = [], []
 for cfg in ("n1024", "cfg2", "n4096"):
     for mod in ("QPSK", "16QAM", "64QAM"):
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--mod", mod, "--no-cpu", "--steps", "100", "--warmup", "5"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--mod", mod, "--full", "--no-cpu", "--steps", "100", "--warmup", "5"],
                              capture_output=True, text=True, timeout=600)
         d = json.loads(out.stdout.strip().splitlines()[-1])
         lines.append(d)
