@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define OFDM_ABI_VERSION 1
+#define OFDM_ABI_VERSION 1    /* additions that leave every existing declaration as it is keep the version (ofdm_fo_demod_frames) */
 
 typedef enum {
     OFDM_OK = 0,
@@ -258,6 +258,38 @@ int ofdm_fo_get_state(ofdm_fo* h, double* h_tsr, float* h_chan_freq, float* h_ch
  * OFDM_ERR_UNBOUND: row 0 of an earlier call fails the data guard before any row passed (:392).
  * h_data_freq_d[100][floor(Kd/DSSS)] complex64 interleaved. */
 int ofdm_fo_get_despread(ofdm_fo* h, float* h_data_freq_d);
+
+/* Frame-batched device path of the same receiver (additive: ofdm_fo_work and the handle's stream state are untouched).
+ * Every frame is the FIRST work() call of a FRESH SynchEstAndFO / SynchEstFOAndDSSS / table-mode instance on that frame's
+ * samples d_iq[f*frame_stride .. +frame_len) (complex64 items).  All pointers below are DEVICE pointers; NULL = not wanted.
+ * R = OFDM_FO_MAX_SYNC rows per frame; row r < n_sync is the r-th accepted sync, rows >= n_sync are written as zeros.
+ * On a fresh first call a trial is evaluated only if S*L + P*stride + N + cp < frame_len (:249), so the data window of every
+ * accepted sync is complete: the reference's ValueError (short slice, :338), UnboundLocalError (DSSS :392) and NameError
+ * (undefined dmax_tmp_ind) cannot occur.  The one per-frame error is a 101st sync (IndexError, :294-296): that frame gets
+ * status OFDM_ERR_INDEX and unspecified other outputs; the other frames and the call's return value are unaffected. */
+typedef struct ofdm_fo_batch_out {
+    int32_t* status;       /* REQUIRED [n_frames]: n_sync (0..R) or OFDM_ERR_INDEX                                        */
+    int32_t* tsr;          /* [n_frames][R][3] time_synch_ref {P*stride+cp, lag, int(max|corr|)}                          */
+    int32_t* fo_idx;       /* [n_frames] dmax_tmp_ind: best candidate of the LAST trial evaluated (:283), -1 if none       */
+    float* data_freq;      /* [n_frames][R][Kd] complex64 est_data_freq: one equalised data symbol per sync (:332-358)      */
+    uint8_t* bits;         /* hard QPSK bits of those rows: [n_frames][R][Kd*2] bytes (UNPACKED) or [..][Kd/4] (PACKED)   */
+    int32_t bits_mode;     /* ofdm_bits_mode of `bits` (PACKED needs num_data_bins % 4 == 0)                               */
+    float* data_freq_d;    /* cfg.dsss > 0 only: [n_frames][R][floor(Kd/DSSS)] complex64 est_data_freq_d (DS:391-399)      */
+    float* chan_freq;      /* [n_frames][R][nfft] complex64 est_chan_freq_P                                                */
+    float* chan_time;      /* [n_frames][R][nfft] complex64 est_chan_time                                                  */
+    float* synch_freq;     /* [n_frames][R][S*Ks] complex64 est_synch_freq                                                 */
+} ofdm_fo_batch_out;
+
+/* Device workspace of ofdm_fo_demod_frames for batches of up to n_frames frames of frame_len samples (grows, never shrinks;
+ * synchronises the device).  Call it before capturing a batch call into a hipGraph. */
+int ofdm_fo_reserve(ofdm_fo* h, int64_t n_frames, int64_t frame_len);
+/* Asynchronous on `stream` (NULL = the handle's stream): four launches -- trial table of every frame, per-frame decision
+ * (gate, distance rule, 101st sync), LS estimate per accepted sync, one data symbol per sync (+ despreading) -- with no host
+ * synchronisation and no allocation once ofdm_fo_reserve covers the call (else the workspace grows first, outside a capture).
+ * Returns R (rows per frame) or a negative ofdm_status; argument errors (NULL handle, NULL status, data_freq_d without dsss,
+ * frame_stride < frame_len, a batch beyond the kernels' index range) return OFDM_ERR_INVALID without touching the device. */
+int64_t ofdm_fo_demod_frames(ofdm_fo* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             const ofdm_fo_batch_out* out, void* stream);
 
 /* ------------------------------------------------ regression-tracking receiver */
 /* Device primitives behind OFDMReceiver.SynchronizeAndEstimate (G/LEGACY/gr-ofdm-rx/python/SynchronizeAndEstimate.py:25-442).

@@ -236,7 +236,26 @@ struct ofdm_fo {
     float* d_trial_m = nullptr;          // [n_fo * TRIAL_WIN]
     int* d_trial_d = nullptr;
     static constexpr int TRIAL_WIN = 256;
+    // ---- frame batch workspace (ofdm_fo_demod_frames)
+    int64_t cap_frames = 0;
+    int64_t cap_table = 0;               // trial-table entries
+    float* b_tm = nullptr;               // [frames][n_fo][trials] max|corr|
+    int* b_td = nullptr;                 //                        argmax lag
+    int* b_tsr = nullptr;                // [frames][100][4] {P*stride+cp, lag, int(max), live}
+    int* b_fo = nullptr;                 // [frames] dmax_tmp_ind (when the caller does not ask for it)
+    cf* b_gain = nullptr;                // [frames][100][Kd]
+    cf* b_edf = nullptr;                 // [frames][100][Kd] est_data_freq for the despreader (dsss > 0 only)
 };
+
+namespace {
+// Trials of a fresh first work() call on n_in samples (SynchEstAndFO.py:246-249, as in ofdm_fo_work): all of them valid.
+int64_t fo_trials(const RxDev& d, int64_t n_in) {
+    const int64_t n_trials = int64_t(std::nearbyint(double(n_in) / double(d.stride)));
+    const int64_t lim = n_in - (int64_t(d.S) * d.L + d.nfft + d.cp);
+    const int64_t p_valid = lim > 0 ? (lim + d.stride - 1) / d.stride : 0;
+    return std::min(p_valid, n_trials);
+}
+}  // namespace
 
 struct ofdm_trk {
     ofdm_trk_cfg cfg{};
@@ -1071,7 +1090,8 @@ int ofdm_fo_destroy(ofdm_fo* h) {
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     void* ptrs[] = {h->d_tw, h->d_zc, h->d_rot, h->d_in, h->t_tsr, h->t_H, h->t_htime, h->t_esf, h->t_gain,
-                    h->t_edf, h->d_code, h->t_edfd, h->s_eqg, h->s_ysc, h->d_trial_m, h->d_trial_d};
+                    h->t_edf, h->d_code, h->t_edfd, h->s_eqg, h->s_ysc, h->d_trial_m, h->d_trial_d,
+                    h->b_tm, h->b_td, h->b_tsr, h->b_fo, h->b_gain, h->b_edf};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1353,6 +1373,148 @@ int ofdm_fo_get_state(ofdm_fo* h, double* h_tsr, float* h_chan_freq, float* h_ch
     if (h_data_freq) HIP_TRY(hipMemcpy(h_data_freq, h->t_edf, R * d.Kd * sizeof(cf), hipMemcpyDeviceToHost));
     if (h_eq_gain) HIP_TRY(hipMemcpy(h_eq_gain, h->s_eqg, size_t(d.Ks) * sizeof(cf), hipMemcpyDeviceToHost));
     return OFDM_OK;
+}
+
+int ofdm_fo_reserve(ofdm_fo* h, int64_t n_frames, int64_t frame_len) {
+    if (!h || n_frames < 0 || frame_len < 0) return fail(OFDM_ERR_INVALID, "ofdm_fo_reserve: bad argument");
+    const int64_t pv = fo_trials(h->dev, frame_len);
+    if (n_frames > INT32_MAX / (8 * OFDM_FO_MAX_SYNC) || pv * h->cfg.n_fo > INT32_MAX / 2)
+        return fail(OFDM_ERR_INVALID, "ofdm_fo_reserve: batch too large");
+    const int64_t table = n_frames * h->cfg.n_fo * pv;
+    if (n_frames <= h->cap_frames && table <= h->cap_table) return OFDM_OK;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipDeviceSynchronize());
+    const int64_t frames = std::max(n_frames, h->cap_frames), tab = std::max(table, h->cap_table);
+    for (void* p : {(void*)h->b_tm, (void*)h->b_td, (void*)h->b_tsr, (void*)h->b_fo, (void*)h->b_gain, (void*)h->b_edf})
+        if (p) (void)hipFree(p);
+    h->b_tm = nullptr;
+    h->b_td = h->b_tsr = h->b_fo = nullptr;
+    h->b_gain = h->b_edf = nullptr;
+    h->cap_frames = h->cap_table = 0;
+    const size_t units = size_t(frames) * OFDM_FO_MAX_SYNC;
+    int rc = dev_alloc(&h->b_tm, size_t(tab));
+    if (rc == OFDM_OK) rc = dev_alloc(&h->b_td, size_t(tab));
+    if (rc == OFDM_OK) rc = dev_alloc(&h->b_tsr, units * 4);
+    if (rc == OFDM_OK) rc = dev_alloc(&h->b_fo, size_t(frames));
+    if (rc == OFDM_OK) rc = dev_alloc(&h->b_gain, units * h->dev.Kd);
+    if (rc == OFDM_OK && h->cfg.dsss > 0) rc = dev_alloc(&h->b_edf, units * h->dev.Kd);
+    if (rc != OFDM_OK) return rc;
+    h->cap_frames = frames;
+    h->cap_table = tab;
+    return OFDM_OK;
+}
+
+int64_t ofdm_fo_demod_frames(ofdm_fo* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             const ofdm_fo_batch_out* out, void* stream) {
+    // checks that need neither the device nor the handle's contents come first
+    if (!h || !out || !out->status) return fail(OFDM_ERR_INVALID, "ofdm_fo_demod_frames: null handle, output set or status");
+    if (n_frames < 0 || frame_len < 0 || frame_stride < frame_len || (n_frames > 0 && !d_iq))
+        return fail(OFDM_ERR_INVALID, "ofdm_fo_demod_frames: bad frame layout");
+    if (out->data_freq_d && h->cfg.dsss <= 0) return fail(OFDM_ERR_INVALID, "data_freq_d needs a handle created with dsss >= 1");
+    const RxDev& d = h->dev;
+    const int N = d.nfft, Kd = d.Kd, n_fo = h->cfg.n_fo;
+    constexpr int R = OFDM_FO_MAX_SYNC;
+    if (out->bits) {
+        if (out->bits_mode != OFDM_BITS_PACKED && out->bits_mode != OFDM_BITS_UNPACKED)
+            return fail(OFDM_ERR_INVALID, "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+        if (out->bits_mode == OFDM_BITS_PACKED && (Kd & 3)) return fail(OFDM_ERR_INVALID, "packed bits need num_data_bins %% 4 == 0");
+    }
+    const int64_t pv = fo_trials(d, frame_len);
+    // index types of the kernels: units (frame, row) as int (x4 in the demod's tsr index), trials x candidates per frame as int
+    if (n_frames > INT32_MAX / (8 * R) || pv * n_fo > INT32_MAX / 2)
+        return fail(OFDM_ERR_INVALID, "ofdm_fo_demod_frames: batch too large (%lld frames, %lld trials x %d candidates)",
+                    (long long)n_frames, (long long)pv, n_fo);
+    if (n_frames == 0) return R;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    if (n_frames > h->cap_frames || n_frames * n_fo * pv > h->cap_table) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            return fail(OFDM_ERR_INVALID, "ofdm_fo_demod_frames: workspace must grow, which cannot happen inside a capture "
+                                          "(call ofdm_fo_reserve first)");
+        const int rc = ofdm_fo_reserve(h, n_frames, frame_len);
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t units = n_frames * R;
+    const cf* iq = reinterpret_cast<const cf*>(d_iq);
+
+    // 1. trial table of every frame, every candidate (FO:248-282), in parts of at most 65535 frames (one grid row per frame)
+    for (int64_t f0 = 0; f0 < n_frames && pv > 0; f0 += 65535) {
+        SyncArgs sa{};
+        sa.iq = iq + f0 * frame_stride;
+        sa.frame_stride = frame_stride;
+        sa.frame_len = frame_len;
+        sa.n_frames = int(std::min<int64_t>(65535, n_frames - f0));
+        sa.mode = 1;
+        sa.p_begin = 0;
+        sa.p_count = int(pv);
+        sa.trial_m = h->b_tm + f0 * n_fo * pv;
+        sa.trial_d = h->b_td + f0 * n_fo * pv;
+        sa.rot = h->d_rot;
+        sa.n_rot = n_fo;
+        HIP_TRY(launch_rx_sync(d, sa, s));
+    }
+    // 2. per-frame decision (FO:282-298): status, time_synch_ref, dmax_tmp_ind, the (frame, row) units
+    int* fo_idx = out->fo_idx ? out->fo_idx : h->b_fo;
+    FoDecideArgs da{};
+    da.trial_m = h->b_tm;
+    da.trial_d = h->b_td;
+    da.n_frames = int(n_frames);
+    da.n_rot = n_fo;
+    da.p_count = int(pv);
+    da.rows = R;
+    da.err_index = OFDM_ERR_INDEX;
+    da.status = out->status;
+    da.tsr_out = out->tsr;
+    da.fo_idx = fo_idx;
+    da.u_tsr = h->b_tsr;
+    HIP_TRY(launch_fo_decide(d, da, s));
+    // 3. LS estimate per accepted sync: sync vector of the LAST candidate, lag of the best one (FO:268-274,300-329)
+    SyncArgs fa{};
+    fa.iq = iq;
+    fa.frame_stride = frame_stride;
+    fa.frame_len = frame_len;
+    fa.n_frames = int(units);
+    fa.tsr = h->b_tsr;
+    fa.H = reinterpret_cast<cf*>(out->chan_freq);
+    fa.gain = h->b_gain;
+    fa.htime = reinterpret_cast<cf*>(out->chan_time);
+    fa.esf = reinterpret_cast<cf*>(out->synch_freq);
+    fa.rot = h->d_rot ? h->d_rot + size_t(n_fo - 1) * N : nullptr;
+    fa.n_rot = 1;
+    HIP_TRY(launch_fo_finalize(d, fa, R, s));
+    // 4. one data symbol per sync at time_synch_ref[0] + S*L, rotated by the frame's LAST trial pick (FO:332-358)
+    cf* edf = reinterpret_cast<cf*>(out->data_freq);
+    if (!edf && out->data_freq_d) edf = h->b_edf;
+    if (edf || out->bits) {
+        DemodArgs ma{};
+        ma.iq = iq;
+        ma.frame_stride = frame_stride;
+        ma.frame_len = frame_len;
+        ma.n_frames = int(units);
+        ma.tsr = h->b_tsr;
+        ma.gain = h->b_gain;
+        ma.eq = edf;
+        ma.bits = out->bits;
+        ma.bits_mode = out->bits ? out->bits_mode : 0;
+        ma.mod = 2;
+        ma.n_dsym = 1;
+        ma.row_stride_pat = 1;
+        ma.rows_per_frame = 1;
+        ma.zero_skipped = 1;
+        ma.rot = h->d_rot;                      // table mode: none
+        ma.units_per_frame = R;
+        ma.rot_idx = fo_idx;
+        HIP_TRY(launch_rx_demod(d, ma, s));
+    }
+    if (out->data_freq_d) {                     // DS:391-399 over every row (zero rows despread to zero)
+        for (int64_t r0 = 0; r0 < units; r0 += 65535) {
+            const int rows = int(std::min<int64_t>(65535, units - r0));
+            HIP_TRY(launch_despread(edf + r0 * Kd, Kd, h->d_code, h->cfg.dsss, h->n_spread, rows,
+                                    reinterpret_cast<cf*>(out->data_freq_d) + r0 * h->n_spread, s));
+        }
+    }
+    return R;
 }
 
 int ofdm_fo_get_despread(ofdm_fo* h, float* h_data_freq_d) {

@@ -30,6 +30,9 @@ struct DemodArgs {
     const cf* rot;           // per-sample rotator e^{j 2pi fo n/fs} [nfft] applied to every window (CFO receiver), or null
     int host_guard;          // 1: a frame is demodulated iff tsr[frame][3] != 0 (the host applied the reference's own guard)
     unsigned* work;          // [2] device words {next chunk, workgroups done}, both 0 between launches: work queue (batch path), or null
+    int units_per_frame;     // > 0: batch CFO receiver -- launch frame u is row u % units_per_frame of IQ frame u / units_per_frame,
+                             // demodulated iff tsr[u][3] != 0 (rows past a frame's syncs are written as zeros); 0 = off
+    const int* rot_idx;      // with units_per_frame and rot: [IQ frames] device candidate index into rot[n_rot][nfft] per frame
 };
 
 // ---- RX sync search + LS estimate (reference: SynchAndChanEst.py:143-219, "Loop A") -----------
@@ -38,7 +41,7 @@ struct SyncArgs {
     int64_t frame_stride;
     int64_t frame_len;
     int n_frames;
-    int mode;                // 0: per-frame sequential search + finalize; 1: trial table only (frame 0)
+    int mode;                // 0: per-frame sequential search + finalize; 1: trial table only, units (frame, candidate, trial)
     int p_begin;
     int p_count;             // mode 0: max trials (<=0: unbounded); mode 1: number of trials in the table
     int force_accept;        // mode 0: accept trial p_begin regardless of the gate (host already decided)
@@ -50,8 +53,8 @@ struct SyncArgs {
     cf* esf;                 // [n_frames][MM]  est_synch_freq row, or null
     cf* eqg;                 // [n_frames][Ks]  eq_gain, or null
     cf* yscratch;            // [n_frames][MM]  raw sync-bin values of the current trial (needed for esf), or null
-    float* trial_m;          // mode 1: [n_rot*p_count] max|corr| (-1 = trial not valid), candidate-major
-    int* trial_d;            // mode 1: [n_rot*p_count] argmax lag
+    float* trial_m;          // mode 1: [n_frames][n_rot][p_count] max|corr| (-1 = trial not valid), candidate-major per frame
+    int* trial_d;            // mode 1: [n_frames][n_rot][p_count] argmax lag
     const cf* rot;           // carrier-offset rotators [n_rot][nfft] (mode 1) / the one rotator of the finalize (mode 0), or null
     int n_rot;               // mode 1: candidates per trial (0 or 1 = plain)
     int off_delta;           // added to the window start P*stride + cp (+L*LL); 0 = the reference layout of SynchAndChanEst
@@ -75,6 +78,21 @@ struct SyncArgs {
                              //   (finalize the first hit unless an early finalize did, report a miss, re-arm seg_state); 2 = early
                              //   finalize behind a first stage the caller runs on its own (a hit there is the first hit: finalize it
                              //   and mark seg_state[1]; nothing found: leave everything to the later stages); 0 = none
+};
+
+// ---- batch CFO receiver (SynchEstAndFO.py:248-358 per frame, fresh instance): the decision the stream block takes on the host
+struct FoDecideArgs {
+    const float* trial_m;    // [n_frames][n_rot][p_count] trial table of rx_sync_kernel mode 1
+    const int* trial_d;
+    int n_frames;
+    int n_rot;
+    int p_count;             // trials per frame (all valid: P*stride < frame_len - (S*L + N + cp), :249)
+    int rows;                // table rows per frame (OFDM_FO_MAX_SYNC)
+    int err_index;           // status of a frame that reaches row `rows` (OFDM_ERR_INDEX)
+    int* status;             // [n_frames] n_sync or err_index
+    int* tsr_out;            // [n_frames][rows][3] {P*stride+cp, lag, int(max|corr|)}, rows >= n_sync zero, or null
+    int* fo_idx;             // [n_frames] best candidate of the last trial (-1: none), or null
+    int* u_tsr;              // [n_frames][rows][4] {P*stride+cp, lag, int(max|corr|), live}: the finalize / demod units
 };
 
 // Segments of the first stage of a staged segment search: a continuing stream finds its sync a few symbols into the buffer, so
@@ -144,6 +162,11 @@ struct ChanArgs {
 
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
+// batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs
+hipError_t launch_fo_decide(const RxDev& rx, const FoDecideArgs& a, hipStream_t s);
+// batch CFO receiver: LS estimate of every (frame, row) unit, a.n_frames = units, units_per_frame rows per IQ frame.  Reads
+// {P*stride+cp, lag, live} from a.tsr (FoDecideArgs::u_tsr); a.rot = the LAST candidate's rotator or null; a.H may be null.
+hipError_t launch_fo_finalize(const RxDev& rx, const SyncArgs& a, int units_per_frame, hipStream_t s);
 // htime[r] = ifft(H[r]) for n_rows rows of nfft bins (est_chan_time on demand)
 hipError_t launch_rx_chan_time(const RxDev& rx, const cf* H, cf* htime, int n_rows, hipStream_t s);
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);

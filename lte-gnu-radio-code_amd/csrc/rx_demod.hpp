@@ -358,6 +358,8 @@ struct DemodGeom {
 enum DemodFlags : unsigned {
     DF_ROT = 1u << 0,            // every window is multiplied by a carrier-offset rotator (SynchEstAndFO.py:339)
     DF_HG = 1u << 1,             // a frame is demodulated iff the host set its guard flag (tracker receiver)
+    DF_UNITS = 1u << 15,         // batch CFO receiver: launch frames are (IQ frame, sync row) units (DemodArgs::units_per_frame),
+                                 // a unit is demodulated iff its tsr[3] is set, the rotator is picked per IQ frame (rot_idx)
     DF_GAINS_GLOBAL = 1u << 2,   // gains re-read from global memory per symbol instead of one LDS copy per chunk
     DF_TEMPORAL_LD = 1u << 3,    // plain (cached) stream loads instead of the non-temporal hint ...
     DF_TEMPORAL_ST = 1u << 11,   // ... and plain equalised-symbol stores (the pair of them is the round-1 / early round-2 kernel)
@@ -375,7 +377,7 @@ enum DemodFlags : unsigned {
 
 template <int N, int MOD, int BMODE, int MINW, unsigned FLAGS = 0>
 __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev rx, DemodArgs a) {
-    constexpr bool ROT = (FLAGS & DF_ROT) != 0, HG = (FLAGS & DF_HG) != 0,
+    constexpr bool ROT = (FLAGS & DF_ROT) != 0, HG = (FLAGS & DF_HG) != 0, UNITS = (FLAGS & DF_UNITS) != 0,
                    GREG = (FLAGS & DF_GAINS_VGPR) != 0 && Plan<N>::T >= 64 && (FLAGS & DF_FOUR_PER_LANE) == 0 && !(MOD == 1 && BMODE == 1),
                    GLDS = (FLAGS & DF_GAINS_GLOBAL) == 0 && !GREG,
                    // The IQ stream is read once and the equalised symbols are written once: both carry the non-temporal hint.
@@ -449,9 +451,12 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
 
     const int Kd = rx.Kd, L = rx.L, S = rx.S, D = rx.D;
     const int tsr0 = a.tsr[frame * 4 + 0];
-    const bool frame_on = HG ? (a.tsr[frame * 4 + 3] != 0) : true;     // host-applied guard (tracker receiver)
+    const bool frame_on = (HG || UNITS) ? (a.tsr[frame * 4 + 3] != 0) : true;     // host-applied guard (tracker) / live unit
+    const int src_frame = UNITS ? frame / a.units_per_frame : frame;
     // L2IN (experiment only, wrong results): every workgroup reads frame (blockIdx % 8) -> the input stays cache-resident
-    const cf* frame_iq = a.iq + int64_t(L2IN ? (blockIdx.x & 7) : frame) * a.frame_stride;
+    const cf* frame_iq = a.iq + int64_t(L2IN ? (blockIdx.x & 7) : src_frame) * a.frame_stride;
+    // batch CFO receiver: every sync of a frame is rotated by the frame's LAST trial pick (SynchEstAndFO.py:339)
+    const cf* rotp = (UNITS && ROT) ? a.rot + int64_t(max(a.rot_idx[src_frame], 0)) * N : a.rot;
 
     // the frame's gains -> LDS, once per chunk (Kd even: whole 16 B pairs); published by the FFT's first barrier
     const cf* gain = a.gain + int64_t(frame) * Kd;
@@ -487,7 +492,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
         sy.valid = active && it < n_iter && ds < ds1;
         const int p = ds / D, n_ = ds - p * D;
         const int64_t pat_ptr = int64_t(tsr0) + int64_t(S) * L * (int64_t(p) * (S + D) + 1);
-        sy.compute = sy.valid && (HG ? frame_on : (pat_ptr + N - 1 <= a.frame_len));
+        sy.compute = sy.valid && (HG ? frame_on : (pat_ptr + N - 1 <= a.frame_len)) && (!UNITS || frame_on);
         sy.start = pat_ptr + int64_t(L) * n_;
         sy.orow = int64_t(frame) * a.rows_per_frame + (p * a.row_stride_pat + n_);
         return sy;
@@ -503,7 +508,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
             for (int n0 = 0; n0 < P; ++n0) v[n0] = NTL ? __builtin_nontemporal_load(src + T * n0) : src[T * n0];
             if constexpr (ROT) {                                         // data_buff_time * cfo[idx]  (SynchEstAndFO.py:339)
 #pragma unroll
-                for (int n0 = 0; n0 < P; ++n0) v[n0] = cmul(v[n0], a.rot[t + T * n0]);
+                for (int n0 = 0; n0 < P; ++n0) v[n0] = cmul(v[n0], rotp[t + T * n0]);
             }
         } else {                                                         // short tail: fft(x, N) zero-pads (:230)
             const int64_t last = a.frame_len > 0 ? a.frame_len - 1 : 0;
@@ -518,7 +523,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
                 const int64_t idx = sy.start + tq + T * n0;
                 const cf x = any ? frame_iq[idx < 0 ? 0 : (idx < last ? idx : last)] : cf{0.f, 0.f};
                 v[n0] = (any && idx >= 0 && idx < a.frame_len) ? x : cf{0.f, 0.f};
-                if constexpr (ROT) v[n0] = cmul(v[n0], a.rot[tq + T * n0]);
+                if constexpr (ROT) v[n0] = cmul(v[n0], rotp[tq + T * n0]);
             }
         }
     };
@@ -873,6 +878,29 @@ hipError_t launch_rx_demod_n(const RxDev& rx, const DemodArgs& a_in, hipStream_t
     if (a.host_guard) {             // tracker receiver: equalised symbols only, frames enabled by the host
         if (bmode != 0 || a.rot) return hipErrorInvalidValue;
         hipLaunchKernelGGL((rx_demod_kernel<N, 2, 0, 3, DF_HG>), dim3(grid), dim3(DG::WG), lds, s, rx, a);
+        return hipGetLastError();
+    }
+    if (a.units_per_frame > 0) {    // batch CFO receiver: QPSK (FO:341-358), optional fused hard bits, no work queue
+        if (a.mod != 2 || a.host_guard || a.work || (a.rot && !a.rot_idx)) return hipErrorInvalidValue;
+#define OFDM_FO_UNITS(B, FL)                                                                                                 \
+    do {                                                                                                                     \
+        if (lds > 65536) {                                                                                                   \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rx_demod_kernel<N, 2, B, 2, DF_UNITS | FL>),   \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));                       \
+            if (e != hipSuccess) return e;                                                                                   \
+        }                                                                                                                    \
+        hipLaunchKernelGGL((rx_demod_kernel<N, 2, B, 2, DF_UNITS | FL>), dim3(grid), dim3(DG::WG), lds, s, rx, a);           \
+    } while (0)
+        if (a.rot) {
+            if (bmode == 0) OFDM_FO_UNITS(0, DF_ROT);
+            else if (bmode == 1) OFDM_FO_UNITS(1, DF_ROT);
+            else OFDM_FO_UNITS(2, DF_ROT);
+        } else {
+            if (bmode == 0) OFDM_FO_UNITS(0, 0u);
+            else if (bmode == 1) OFDM_FO_UNITS(1, 0u);
+            else OFDM_FO_UNITS(2, 0u);
+        }
+#undef OFDM_FO_UNITS
         return hipGetLastError();
     }
     if (a.rot) {                    // CFO receiver: equalised symbols only

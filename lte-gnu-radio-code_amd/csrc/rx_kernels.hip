@@ -164,7 +164,8 @@ __device__ __forceinline__ void sync_trial(const RxDev& rx, const cf* frame_iq, 
 
 // ---- finalize (:171-218): LS estimate on the sync bins, equaliser gains, channel impulse response.
 // Shared by the sequential and the screened search kernels; Zs .. dhats describe the accepted trial (zeros if none).
-template <int N, class TW>
+// OPT_H (batch CFO receiver only): est_chan_freq_P is an optional output, a.H may be null.
+template <int N, class TW, bool OPT_H = false>
 __device__ __forceinline__ void sync_finalize(const RxDev& rx, const SyncArgs& a, int frame, bool active, bool found, int Phit,
                                               const cf (&Zs)[Plan<N>::P], cf zdups, float pests, float ms, int dhats, cf* lds,
                                               const TW& tw, const cf* w1tab, int t, cf* ysc) {
@@ -231,7 +232,7 @@ __device__ __forceinline__ void sync_finalize(const RxDev& rx, const SyncArgs& a
         if (found && pos) Hk = Hp;
         lds[k] = Hk;                               // natural-order H for the est_chan_time inverse FFT below (same lane, same slot)
         if (active) {
-            a.H[int64_t(frame) * N + k] = Hk;
+            if (!OPT_H || a.H) a.H[int64_t(frame) * N + k] = Hk;
             if (a.eqg || a.esf) {
                 // eq_gain = conj(chan_est)/(|chan_est|^2 + 1/snr) (:213-216); est_synch_freq = eq_gain * r (:217-218)
                 if (neg) {
@@ -311,7 +312,9 @@ __global__ void __launch_bounds__(Plan<N>::WG) rx_chan_time_kernel(RxDev rx, con
     }
 }
 
-template <int N, int MINW = 3>
+// TABLE: the trial table (mode 1) of a frame batch only -- frame = blockIdx.y -- without the mode-0 search and finalize, so that
+// its register budget is that of one trial (batch CFO receiver).  TABLE = false is the stream blocks' kernel with both modes.
+template <int N, int MINW = 3, bool TABLE = false>
 __global__ void __launch_bounds__(Plan<N>::WG, MINW) rx_sync_kernel(RxDev rx, SyncArgs a) {
     using PL = Plan<N>;
     constexpr int T = PL::T, P = PL::P;
@@ -330,8 +333,9 @@ __global__ void __launch_bounds__(Plan<N>::WG, MINW) rx_sync_kernel(RxDev rx, Sy
 
     const int64_t unit = int64_t(blockIdx.x) * PL::SLOTS + slot;
 
-    if (a.mode == 1) {
-        // ---- trial table for the stream block: unit = trial index, frame 0
+    if (TABLE || a.mode == 1) {
+        // ---- trial table: unit = cand * p_count + trial of frame blockIdx.y (TABLE) / of frame 0 (the stream blocks)
+        const int64_t frame = TABLE ? int64_t(blockIdx.y) : 0;
         const int n_rot = a.n_rot > 1 ? a.n_rot : 1;
         const bool active = unit < int64_t(a.p_count) * n_rot;
         const int cand = active ? int(unit / a.p_count) : 0;            // candidate-major: unit = cand * p_count + w
@@ -342,10 +346,12 @@ __global__ void __launch_bounds__(Plan<N>::WG, MINW) rx_sync_kernel(RxDev rx, Sy
         cf zdup;
         float p_est, m;
         int dhat;
-        sync_trial<N>(rx, a.iq, a.frame_len, valid, Ptrial, lds, red, tw, w1tab, t, Z, zdup, p_est, m, dhat, nullptr, rot, a.off_delta);
+        sync_trial<N>(rx, a.iq + frame * a.frame_stride, a.frame_len, valid, Ptrial, lds, red, tw, w1tab, t, Z, zdup, p_est, m, dhat,
+                      nullptr, rot, a.off_delta);
         if (active && t == 0) {
-            a.trial_m[unit] = valid ? m : -1.f;
-            a.trial_d[unit] = valid ? dhat : 0;
+            const int64_t o = frame * a.p_count * n_rot + unit;
+            a.trial_m[o] = valid ? m : -1.f;
+            a.trial_d[o] = valid ? dhat : 0;
         }
         return;
     }
@@ -413,6 +419,151 @@ __global__ void __launch_bounds__(Plan<N>::WG, MINW) rx_sync_kernel(RxDev rx, Sy
     }
 
     sync_finalize<N>(rx, a, frame, active, found, Phit, Zs, zdups, pests, ms, dhats, lds, tw, w1tab, t, ysc);
+}
+
+// ------------------------------------------------------------------------------------------ batch CFO receiver
+// What ofdm_fo_work decides on the host between its trial-table and finalize launches (SynchEstAndFO.py:282-298), for every
+// frame of a batch at once: one wave per frame.  Per trial the best candidate (first maximum, strict >, :282-285); the trials
+// that pass the gate (:288) are walked in order, 64 at a time from a ballot, by one lane that applies the distance rule
+// against the previous accepted sync (:289-291, no break) and stops the frame at a 101st sync (:294-296).
+__global__ void __launch_bounds__(64) fo_decide_kernel(RxDev rx, FoDecideArgs a) {
+    __shared__ float s_m[64];
+    __shared__ int s_d[64];
+    __shared__ int s_state[3];                           // {rows accepted, last accepted window start, error}
+    const int frame = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t base = int64_t(frame) * a.n_rot * a.p_count;
+    const float* tm = a.trial_m + base;
+    const int* td = a.trial_d + base;
+    if (lane == 0) {
+        s_state[0] = 0;
+        s_state[1] = 0;
+        s_state[2] = 0;
+    }
+    __syncthreads();
+    int last_best = -1;                                  // :283 dmax_tmp_ind of the last trial (lane (p_count-1) % 64 holds it)
+    const int64_t row0 = int64_t(frame) * a.rows;
+    for (int p0 = 0; p0 < a.p_count; p0 += 64) {
+        const int w = p0 + lane;
+        const bool in = w < a.p_count;
+        int best = 0;
+        float bm = in ? tm[w] : 0.f;
+        int bd = in ? td[w] : 0;
+        for (int c = 1; c < a.n_rot; ++c) {
+            const float v = in ? tm[int64_t(c) * a.p_count + w] : 0.f;
+            if (v > bm) {
+                bm = v;
+                best = c;
+                bd = td[int64_t(c) * a.p_count + w];
+            }
+        }
+        if (in) last_best = best;
+        const bool pass = in && bm > rx.gate_mm;
+        unsigned long long mask = __ballot(pass);
+        s_m[lane] = bm;
+        s_d[lane] = bd;
+        __syncthreads();
+        if (lane == 0 && !s_state[2]) {
+            int n = s_state[0], last = s_state[1];
+            while (mask) {
+                const int b = __ffsll(static_cast<long long>(mask)) - 1;
+                mask &= mask - 1;
+                const int pos = (p0 + b) * rx.stride + rx.cp;
+                if (!(n == 0 || pos - last > 2 * rx.cp + rx.nfft)) continue;                  // :291
+                if (n >= a.rows) {                                                              // :294-296 IndexError
+                    s_state[2] = 1;
+                    break;
+                }
+                const int lag = s_d[b], mi = int(s_m[b]);
+                if (a.tsr_out) {
+                    int* o = a.tsr_out + (row0 + n) * 3;
+                    o[0] = pos;
+                    o[1] = lag;
+                    o[2] = mi;
+                }
+                int* u = a.u_tsr + (row0 + n) * 4;
+                u[0] = pos;
+                u[1] = lag;
+                u[2] = mi;
+                u[3] = 1;
+                ++n;
+                last = pos;
+            }
+            s_state[0] = n;
+            s_state[1] = last;
+        }
+        __syncthreads();
+    }
+    // the last trial's pick sits in lane (p_count - 1) % 64 of the final pass
+    const int src = a.p_count > 0 ? (a.p_count - 1) % 64 : 0;
+    last_best = __shfl(last_best, src);
+    const int n_sync = s_state[0];
+    const bool err = s_state[2] != 0;
+    if (lane == 0) {
+        a.status[frame] = err ? a.err_index : n_sync;
+        if (a.fo_idx) a.fo_idx[frame] = a.p_count > 0 ? last_best : -1;
+    }
+    // rows past the last sync: zero (an erroring frame keeps no live unit at all)
+    for (int r = (err ? 0 : n_sync) + lane; r < a.rows; r += 64) {
+        int* u = a.u_tsr + (row0 + r) * 4;
+        u[0] = 0;
+        u[1] = 0;
+        u[2] = 0;
+        u[3] = 0;
+        if (a.tsr_out && r >= n_sync) {
+            int* o = a.tsr_out + (row0 + r) * 3;
+            o[0] = 0;
+            o[1] = 0;
+            o[2] = 0;
+        }
+    }
+}
+
+// LS estimate of one accepted sync per (frame, row) unit: the finalize launch of ofdm_fo_work (sync vector of the LAST candidate,
+// lag of the best one, FO:268-274,300-329) with the trial and lag read from the decide kernel's table.  The same device functions
+// as rx_sync_kernel mode 0 with force_accept, so the same numbers.  Units past a frame's syncs write zero rows; a workgroup with
+// no live unit writes them without running the trial.
+template <int N, int MINW>
+__global__ void __launch_bounds__(Plan<N>::WG, MINW) rx_fo_finalize_kernel(RxDev rx, SyncArgs a, int units_per_frame) {
+    using PL = Plan<N>;
+    constexpr int T = PL::T, P = PL::P;
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const int tid = threadIdx.x;
+    const int slot = (T >= 64) ? __builtin_amdgcn_readfirstlane(tid / T) : tid / T;
+    const int t = tid % T;
+    const int64_t unit = int64_t(blockIdx.x) * PL::SLOTS + slot;
+    const bool active = unit < a.n_frames;
+    const int64_t u = active ? unit : 0;
+    const int* ut = a.tsr + u * 4;
+    const int pos = active ? ut[0] : 0, lag = active ? ut[1] : 0;
+    const bool live = active && ut[3] != 0;
+    const int Ptrial = (pos - rx.cp) / rx.stride;
+    cf* ysc = a.esf ? a.esf + u * rx.MM : nullptr;      // raw sync-bin values go where est_synch_freq is formed from them, in place
+    if (!__syncthreads_or(live ? 1 : 0)) {
+        if (active) {
+            for (int k = t; k < N; k += T) {
+                if (a.H) a.H[u * N + k] = cf{0.f, 0.f};
+                if (a.htime) a.htime[u * N + k] = cf{0.f, 0.f};
+            }
+            if (a.esf)
+                for (int k = t; k < rx.MM; k += T) a.esf[u * rx.MM + k] = cf{0.f, 0.f};
+        }
+        return;
+    }
+    cf* smem = reinterpret_cast<cf*>(smem_raw);
+    cf* lds = smem + slot * WgLds<N>::STRIDE;
+    float* red = reinterpret_cast<float*>(lds + WgLds<N>::ELEMS);
+    const cf* w1tab = wg_init_w1<N>(smem, rx.tw, tid);
+    std::conditional_t<PL::R0 == 16, CompactTwiddles<N>, LaneTwiddles<N>> tw;
+    load_twiddles(tw, rx.tw, t);
+    const cf* frame_iq = a.iq + (u / units_per_frame) * a.frame_stride;
+    const bool valid = live && int64_t(rx.S) * rx.L + int64_t(Ptrial) * rx.stride + N + rx.cp < a.frame_len;   // :249 (defensive)
+    cf Z[P];
+    cf zdup;
+    float p_est, m;
+    int dhat;
+    sync_trial<N>(rx, frame_iq, a.frame_len, valid, Ptrial, lds, red, tw, w1tab, t, Z, zdup, p_est, m, dhat, ysc, a.rot, 0);
+    sync_finalize<N, decltype(tw), true>(rx, a, int(u), active, valid, Ptrial, Z, zdup, p_est, m, lag, lds, tw, w1tab, t, ysc);
 }
 
 // ------------------------------------------------------------------------------------------ screened sync search
@@ -1468,6 +1619,14 @@ static hipError_t launch_sync_n(const RxDev& rx, const SyncArgs& a, hipStream_t 
     }
     // 3 waves per SIMD (168 VGPRs, a few spills off the trial path): 0.14 ms instead of 0.21 ms per 4369-frame launch; the
     // unconstrained build takes 192 VGPRs + 256 AGPRs (1 wave per SIMD), a 128-register build spills into the trial (0.20 ms)
+    if (a.mode == 1 && a.n_frames > 1) {
+        // trial table of a frame batch: one grid row per frame (gridDim.y <= 65535: the batch CFO path launches larger batches in parts)
+        if (a.n_frames > 65535) return hipErrorInvalidValue;
+        // 1024 / 2048-pt: 2 waves per SIMD keep the trial off scratch (3 spill 6 / 9 VGPRs)
+        constexpr int TMW = (N == 1024 || N == 2048) ? 2 : 3;
+        hipLaunchKernelGGL((rx_sync_kernel<N, TMW, true>), dim3(grid, unsigned(a.n_frames)), dim3(Plan<N>::WG), WgLds<N>::BYTES, s, rx, a);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((rx_sync_kernel<N, 3>), dim3(grid), dim3(Plan<N>::WG), WgLds<N>::BYTES, s, rx, a);
     return hipGetLastError();
 }
@@ -1491,6 +1650,27 @@ hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s) {
 }
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s) {
 #define CALL(n) launch_sync_n<n>(rx, a, s)
+    OFDM_DISPATCH_N(rx.nfft, CALL)
+#undef CALL
+}
+hipError_t launch_fo_decide(const RxDev& rx, const FoDecideArgs& a, hipStream_t s) {
+    if (a.n_frames <= 0) return hipSuccess;
+    if (!a.status || !a.u_tsr || a.rows <= 0 || a.n_rot < 1 || a.p_count < 0 || (a.p_count > 0 && (!a.trial_m || !a.trial_d)))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fo_decide_kernel, dim3(unsigned(a.n_frames)), dim3(64), 0, s, rx, a);
+    return hipGetLastError();
+}
+// 2 waves per SIMD: the trial and the finalize of one unit stay in registers (no scratch; a unit runs once per sync)
+template <int N>
+static hipError_t launch_fo_finalize_n(const RxDev& rx, const SyncArgs& a, int units_per_frame, hipStream_t s) {
+    const unsigned grid = unsigned((int64_t(a.n_frames) + Plan<N>::SLOTS - 1) / Plan<N>::SLOTS);
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL((rx_fo_finalize_kernel<N, 2>), dim3(grid), dim3(Plan<N>::WG), WgLds<N>::BYTES, s, rx, a, units_per_frame);
+    return hipGetLastError();
+}
+hipError_t launch_fo_finalize(const RxDev& rx, const SyncArgs& a, int units_per_frame, hipStream_t s) {
+    if (units_per_frame < 1 || !a.tsr || !a.gain) return hipErrorInvalidValue;
+#define CALL(n) launch_fo_finalize_n<n>(rx, a, units_per_frame, s)
     OFDM_DISPATCH_N(rx.nfft, CALL)
 #undef CALL
 }

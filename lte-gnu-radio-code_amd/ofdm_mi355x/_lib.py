@@ -63,6 +63,13 @@ class FoReport(C.Structure):
                 ("n_data_items", C.c_int64)]
 
 
+class FoBatchOut(C.Structure):
+    """ofdm_fo_batch_out: device pointers (None = not wanted; status is required)."""
+    _fields_ = [("status", C.c_void_p), ("tsr", C.c_void_p), ("fo_idx", C.c_void_p), ("data_freq", C.c_void_p),
+                ("bits", C.c_void_p), ("bits_mode", C.c_int32), ("data_freq_d", C.c_void_p), ("chan_freq", C.c_void_p),
+                ("chan_time", C.c_void_p), ("synch_freq", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -102,6 +109,9 @@ PROTOTYPES = {
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),
     "ofdm_fo_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ofdm_fo_get_despread": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ofdm_fo_reserve": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "ofdm_fo_demod_frames": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(FoBatchOut),
+                                         C.c_void_p]),
     "ofdm_trk_create": (C.c_int, [C.POINTER(TrkCfg), C.POINTER(C.c_void_p)]),
     "ofdm_trk_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_trk_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),

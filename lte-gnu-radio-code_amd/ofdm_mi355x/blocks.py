@@ -214,6 +214,33 @@ class _SyncTableBlock(sync_block):
     def _dump_name(self, date_time):
         return str(self.directory_name) + str(self.file_name_cest) + date_time + '.pckl'         # FO:312
 
+    def demod_frames(self, iq):
+        """Frame batch on the GPU: iq [n_frames, frame_len] complex64, every frame processed as the FIRST work() call of a
+        FRESH instance of this block.  Returns numpy arrays per frame: status (n_sync, or OFDM_ERR_INDEX for a 101st sync),
+        time_synch_ref [100][3] int32, dmax_tmp_ind (-1: no trial), est_data_freq [100][Kd], hard_bits [100][2 Kd] (QPSK,
+        one bit per byte), est_chan_freq_P / est_chan_time [100][nfft], est_synch_freq [100][S*Ks] and, for the DSSS block,
+        est_data_freq_d.  Rows >= n_sync are zero.  The block's own stream state (count, cor_obs, tables) is not touched."""
+        iq = np.ascontiguousarray(iq, dtype=np.complex64)
+        if iq.ndim != 2:
+            raise ValueError("iq must be [n_frames, frame_len]")
+        n, fl = iq.shape
+        R, N, Kd, mm = _lib.FO_MAX_SYNC, self.nfft, self.num_data_bins, self.MM
+        ns = self._engine.n_spread
+        dev = _device()
+        shapes = dict(status=((n,), np.int32), time_synch_ref=((n, R, 3), np.int32), dmax_tmp_ind=((n,), np.int32),
+                      est_data_freq=((n, R, Kd), np.complex64), hard_bits=((n, R, 2 * Kd), np.uint8),
+                      est_chan_freq_P=((n, R, N), np.complex64), est_chan_time=((n, R, N), np.complex64),
+                      est_synch_freq=((n, R, mm), np.complex64))
+        if ns:
+            shapes["est_data_freq_d"] = ((n, R, ns), np.complex64)
+        bufs = {k: DeviceBuffer(max(8, int(np.prod(sh)) * np.dtype(dt).itemsize), dev) for k, (sh, dt) in shapes.items()}
+        d_iq = DeviceBuffer(max(8, iq.nbytes), dev).upload(iq)
+        self._engine.demod_frames(d_iq, n, fl, fl, bufs["status"], d_tsr=bufs["time_synch_ref"], d_fo_idx=bufs["dmax_tmp_ind"],
+                                  d_data_freq=bufs["est_data_freq"], d_bits=bufs["hard_bits"], bits_mode=_lib.BITS_UNPACKED,
+                                  d_data_freq_d=bufs.get("est_data_freq_d"), d_chan_freq=bufs["est_chan_freq_P"],
+                                  d_chan_time=bufs["est_chan_time"], d_synch_freq=bufs["est_synch_freq"])
+        return {k: bufs[k].download(dt, int(np.prod(sh))).reshape(sh) for k, (sh, dt) in shapes.items()}
+
     def work(self, input_items, output_items):
         in0 = input_items[0]
         out = output_items[0]

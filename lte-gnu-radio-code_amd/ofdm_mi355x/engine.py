@@ -226,6 +226,24 @@ class FoEngine:
         check(self.lib.ofdm_fo_get_despread(self._h, ptr(out)))
         return out
 
+    # ---- frame batches on device buffers (each frame: first work() call of a fresh instance) ----------------------
+    def reserve(self, n_frames: int, frame_len: int):
+        check(self.lib.ofdm_fo_reserve(self._h, int(n_frames), int(frame_len)))
+
+    def demod_frames(self, d_iq, n_frames, frame_stride, frame_len, d_status, d_tsr=None, d_fo_idx=None, d_data_freq=None,
+                     d_bits=None, bits_mode=BITS_NONE, d_data_freq_d=None, d_chan_freq=None, d_chan_time=None,
+                     d_synch_freq=None, stream=None) -> int:
+        """ofdm_fo_demod_frames on device buffers; returns the rows per frame (FO_MAX_SYNC).  Per frame: status = n_sync or
+        OFDM_ERR_INDEX (a 101st sync), tsr [100][3] int32, fo_idx int32, data_freq [100][Kd] complex64, bits, data_freq_d
+        [100][Kd/DSSS], chan_freq / chan_time [100][nfft], synch_freq [100][S*Ks]; rows >= n_sync are zero."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.FoBatchOut(addr(d_status), addr(d_tsr), addr(d_fo_idx), addr(d_data_freq), addr(d_bits), int(bits_mode),
+                              addr(d_data_freq_d), addr(d_chan_freq), addr(d_chan_time), addr(d_synch_freq))
+        return int(check(self.lib.ofdm_fo_demod_frames(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
+                                                       C.byref(out), ptr(stream))))
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.ofdm_fo_destroy(self._h)
