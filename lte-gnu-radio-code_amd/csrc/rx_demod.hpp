@@ -175,8 +175,10 @@ __device__ __forceinline__ unsigned pack4(const cf (&z)[4]) {
 #undef OFDM_Q64
     } else if constexpr (MOD == 2) {
         constexpr float t = 1.41421354f;             // largest float32 below sqrt(2): BitRecovery's outlier edge
-        // a coordinate that is exactly zero (a tie of the reference's nearest-point search) takes the literal path
-        if (z[0].x * z[0].y * z[1].x * z[1].y == 0.f || z[2].x * z[2].y * z[3].x * z[3].y == 0.f) {
+        // a coordinate that is exactly zero (a tie of the reference's nearest-point search) takes the literal path.  The
+        // product of a group with a zero is 0, or NaN when another coordinate is inf / NaN or the product overflows first
+        // (inf * 0): !(|p| > 0) is one compare, as == 0 was, and true for both.
+        if (!(fabsf(z[0].x * z[0].y * z[1].x * z[1].y) > 0.f) || !(fabsf(z[2].x * z[2].y * z[3].x * z[3].y) > 0.f)) {
             bool tie = false;
 #pragma unroll
             for (int e = 0; e < 4; ++e) tie |= (z[e].x == 0.f) | (z[e].y == 0.f);
@@ -263,7 +265,8 @@ __device__ __forceinline__ unsigned pack2(const cf (&z)[2]) {
     } else {                                         // MOD == 2
         constexpr float t = 1.41421354f;             // largest float32 below sqrt(2): BitRecovery's outlier edge
         // a coordinate that is exactly zero (a tie of the reference's nearest-point search) takes the literal path
-        if (z[0].x * z[0].y * z[1].x * z[1].y == 0.f) {
+        // (0 or NaN product: see pack4)
+        if (!(fabsf(z[0].x * z[0].y * z[1].x * z[1].y) > 0.f)) {
             const bool tie = (z[0].x == 0.f) | (z[0].y == 0.f) | (z[1].x == 0.f) | (z[1].y == 0.f);
             if (tie) return (hard_bits<2>(z[0]) << 2) | hard_bits<2>(z[1]);
         }
