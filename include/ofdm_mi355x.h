@@ -147,6 +147,41 @@ int ofdm_rx_reserve(ofdm_rx* h, int64_t n_frames);
 int ofdm_demap(ofdm_rx* h, const float* d_sym, int64_t n, int32_t modulation, uint8_t* d_hard,
                float* d_soft0, float* d_soft1, void* stream);
 
+/* Segmented soft de-mapper: ofdm_demap's soft outputs for many buffers in one call, each with ITS OWN sigma.  Segment s is
+ * seg_len complex64 symbols at d_sym + s*seg_stride (complex items); its outputs are exactly what ofdm_demap defines for that
+ * segment alone: sigma_s = 0.7071067811865476 * mean_i dmin(z_i) (nearest-point distance, :88,102), soft0 / soft1 = llrp0 /
+ * llrp1 with hf = -0.5/sigma_s^2 (QPSK literally as :105-125, 16/64-QAM by the per-axis PAM rule of ofdm_demap), bit order
+ * b0..b(bps-1) per symbol, dense [n_seg][seg_len*bps] float32.  llr = soft0 - soft1 in fp32 from the two values the same call
+ * produces: the max-log log(P(b=0)/P(b=1)), positive favours bit 0.  Non-finite or zero-sigma input gives what IEEE arithmetic
+ * of the same formulas gives.  Deterministic: sigma is summed per (segment, slice of 2048 symbols) and the partials are added
+ * in a fixed order, so a segment's outputs are the same bits alone, in any batch and on every call.  DEVICE pointers;
+ * NULL = not wanted. */
+typedef struct ofdm_soft_out {
+    float*  soft0;    /* [n_seg][seg_len*bps] llrp0, or NULL                  */
+    float*  soft1;    /* [n_seg][seg_len*bps] llrp1, or NULL                  */
+    float*  llr;      /* [n_seg][seg_len*bps] soft0 - soft1 (fp32), or NULL   */
+    double* sigma;    /* [n_seg] sigma_s (a per-segment noise estimate), or NULL */
+} ofdm_soft_out;
+
+/* Device workspace of the segmented de-mapper for n_seg segments of seg_len symbols (grows, never shrinks; synchronises the
+ * device).  Call it before capturing ofdm_demap_frames / ofdm_rx_demod_frames_soft into a hipGraph. */
+int ofdm_rx_reserve_soft(ofdm_rx* h, int64_t n_seg, int64_t seg_len);
+/* Asynchronous on `stream` (NULL = the handle's stream): two launches, no host synchronisation and no allocation once
+ * ofdm_rx_reserve_soft covers the call (else the workspace grows first, outside a capture).  modulation 2, 4 or 6 (BPSK:
+ * OFDM_ERR_INVALID, as ofdm_demap).  n_seg == 0, seg_len == 0 or an `out` without any pointer is a no-op returning OFDM_OK.
+ * Argument errors (NULL handle, negative count, seg_stride < seg_len, a batch beyond the kernels' index range) return
+ * OFDM_ERR_INVALID without touching the device. */
+int ofdm_demap_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg_len, int64_t seg_stride,
+                      int32_t modulation, const ofdm_soft_out* out, void* stream);
+/* ofdm_rx_demod_frames with the same arguments (same d_eq / d_bits / d_tsr bits, same return value n_dsym), then
+ * ofdm_demap_frames over d_eq with one segment per frame: seg_len = seg_stride = n_dsym*Kd, modulation = cfg.modulation.
+ * A frame's segment holds every row ofdm_rx_demod_frames writes, the zero rows of guard-failed patterns and of frames without
+ * a sync included.  soft == NULL or without any pointer: exactly ofdm_rx_demod_frames.  Soft outputs need d_eq (the soft
+ * pass reads it); argument errors return OFDM_ERR_INVALID before anything is enqueued. */
+int64_t ofdm_rx_demod_frames_soft(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride,
+                                  int64_t frame_len, float* d_eq, uint8_t* d_bits, int32_t bits_mode,
+                                  int32_t* d_tsr, const ofdm_soft_out* soft, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

@@ -193,6 +193,8 @@ struct ofdm_rx {
     cf* f_H = nullptr;
     cf* f_gain = nullptr;
     cf* f_htime = nullptr;
+    double* f_seg_partial = nullptr;     // [n_seg][seg_slices(seg_len)] sigma partials of ofdm_demap_frames
+    int64_t cap_seg_partial = 0;
     int max_trials = 0;
     int scan_block = 0;                  // > 0: the batch path's sync search is screened in blocks of this many trials
     cf* d_scan_g = nullptr;              // [N + 2] recurrence kernel G, then {max |G|, 0}
@@ -343,7 +345,7 @@ int ofdm_rx_destroy(ofdm_rx* h) {
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     void* ptrs[] = {h->d_pack, h->d_tw,    h->d_zc,  h->d_in,  h->d_edf,     h->s_tsr,     h->s_H,       h->s_htime, h->s_esf, h->s_eqg,
                     h->s_gain,  h->s_ysc, h->d_trial_m, h->d_trial_d, h->d_partial, h->f_tsr, h->f_H, h->f_gain, h->f_htime,
-                    h->d_scan_g, h->d_seg_state, h->d_work};
+                    h->d_scan_g, h->d_seg_state, h->d_work, h->f_seg_partial};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev)
@@ -1063,6 +1065,119 @@ int ofdm_demap(ofdm_rx* h, const float* d_sym, int64_t n, int32_t modulation, ui
     a.partial = h->d_partial;
     HIP_TRY(launch_demap(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
     return OFDM_OK;
+}
+
+// ---- segmented soft de-mapper (one sigma per segment = per frame of the batch path)
+namespace {
+// Index range of the segmented kernels: 64-bit throughout; the bounds keep every product of them inside int64.
+constexpr int64_t SEG_MAX_N = int64_t(1) << 31;      // segments
+constexpr int64_t SEG_MAX_LEN = int64_t(1) << 40;    // symbols per segment, and n_seg*seg_stride
+bool soft_wanted(const ofdm_soft_out* o) { return o && (o->soft0 || o->soft1 || o->llr || o->sigma); }
+// argument check shared by both entry points (no device access); "" = fine
+const char* soft_bad_args(int64_t n_seg, int64_t seg_len, int64_t seg_stride) {
+    if (n_seg < 0 || seg_len < 0) return "negative count";
+    if (seg_stride < seg_len) return "seg_stride < seg_len";
+    if (n_seg > SEG_MAX_N || seg_len > SEG_MAX_LEN || (n_seg > 0 && seg_stride > SEG_MAX_LEN / n_seg))
+        return "batch beyond the kernels' index range";
+    return "";
+}
+// grows the partial-sum workspace; refuses inside a stream capture (growing synchronises and allocates)
+int soft_ensure(ofdm_rx* h, int64_t n_seg, int64_t seg_len, hipStream_t s, const char* who) {
+    if (n_seg * seg_slices(seg_len) <= h->cap_seg_partial) return OFDM_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(OFDM_ERR_INVALID, "%s: workspace must grow, which cannot happen inside a capture (call ofdm_rx_reserve_soft first)",
+                    who);
+    return ofdm_rx_reserve_soft(h, n_seg, seg_len);
+}
+int soft_launch(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg_len, int64_t seg_stride, int32_t modulation,
+                const ofdm_soft_out* out, hipStream_t s) {
+    SegDemapArgs a{};
+    a.sym = reinterpret_cast<const cf*>(d_sym);
+    a.n_seg = n_seg;
+    a.seg_len = seg_len;
+    a.seg_stride = seg_stride;
+    a.n_slices = seg_slices(seg_len);
+    a.mod = modulation;
+    a.soft0 = out->soft0;
+    a.soft1 = out->soft1;
+    a.llr = out->llr;
+    a.sigma = out->sigma;
+    a.partial = h->f_seg_partial;
+    HIP_TRY(launch_demap_frames(a, s));
+    return OFDM_OK;
+}
+}  // namespace
+
+int ofdm_rx_reserve_soft(ofdm_rx* h, int64_t n_seg, int64_t seg_len) {
+    if (!h || n_seg < 0 || seg_len < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_soft: bad argument");
+    if (n_seg > SEG_MAX_N || seg_len > SEG_MAX_LEN) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_soft: batch too large");
+    const int64_t need = n_seg * seg_slices(seg_len);
+    if (need <= h->cap_seg_partial) return OFDM_OK;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipDeviceSynchronize());
+    if (h->f_seg_partial) (void)hipFree(h->f_seg_partial);
+    h->f_seg_partial = nullptr;
+    h->cap_seg_partial = 0;
+    const int rc = dev_alloc(&h->f_seg_partial, size_t(need));
+    if (rc != OFDM_OK) return rc;
+    h->cap_seg_partial = need;
+    return OFDM_OK;
+}
+
+int ofdm_demap_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg_len, int64_t seg_stride, int32_t modulation,
+                      const ofdm_soft_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: null handle");
+    const char* bad = soft_bad_args(n_seg, seg_len, seg_stride);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: %s", bad);
+    if (modulation != 2 && modulation != 4 && modulation != 6)
+        return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)");
+    if (n_seg == 0 || seg_len == 0 || !soft_wanted(out)) return OFDM_OK;
+    if (!d_sym) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: null d_sym");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    const int rc = soft_ensure(h, n_seg, seg_len, s, "ofdm_demap_frames");
+    if (rc != OFDM_OK) return rc;
+    return soft_launch(h, d_sym, n_seg, seg_len, seg_stride, modulation, out, s);
+}
+
+int64_t ofdm_rx_demod_frames_soft(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                  float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr, const ofdm_soft_out* soft,
+                                  void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: null handle");
+    if (!d_iq || n_frames < 0 || frame_len < 0 || frame_stride < frame_len)
+        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: bad argument");
+    const bool want = soft_wanted(soft);
+    if (want && !d_eq) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: soft outputs need d_eq (the soft pass reads it)");
+    const int mod = h->cfg.modulation;
+    if (want && mod != 2 && mod != 4 && mod != 6)
+        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: soft metrics need QPSK, 16-QAM or 64-QAM");
+    const RxDev& d = h->dev;
+    const int64_t n_dsym = frame_len / d.L / (d.S + d.D) * d.D;
+    const int64_t seg_len = n_dsym * d.Kd;
+    // the checks ofdm_rx_demod_frames makes, made here first so that a bad call enqueues nothing
+    if (n_frames > INT32_MAX / 8 || n_dsym > INT32_MAX / 8) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: batch too large");
+    if (d_bits) {
+        if (bits_mode != OFDM_BITS_PACKED && bits_mode != OFDM_BITS_UNPACKED)
+            return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+        if (bits_mode == OFDM_BITS_PACKED && ((d.Kd & 3) || (d.bps & 1)))
+            return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: packed bits need num_data_bins %% 4 == 0 and an even number of bits per symbol");
+    }
+    if (want) {
+        const char* bad = soft_bad_args(n_frames, seg_len, seg_len);
+        if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: %s", bad);
+    }
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    if (want && n_frames > 0 && seg_len > 0) {              // grow first: nothing is enqueued unless the whole call can run
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        int rc = soft_ensure(h, n_frames, seg_len, s, "ofdm_rx_demod_frames_soft");
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t r = ofdm_rx_demod_frames(h, d_iq, n_frames, frame_stride, frame_len, d_eq, d_bits, bits_mode, d_tsr, stream);
+    if (r < 0 || !want || n_frames == 0 || seg_len == 0) return r;
+    const int rc = soft_launch(h, d_eq, n_frames, seg_len, seg_len, mod, soft, s);
+    return rc != OFDM_OK ? rc : r;
 }
 
 int ofdm_bandwidth_probe(int32_t device, const void* d_in, void* d_out, int64_t bytes, int32_t mode, int32_t sym_in_bytes,

@@ -110,6 +110,25 @@ struct DemapArgs {
 };
 constexpr int DEMAP_PARTIALS = 256;
 
+// ---- segmented soft de-mapper (ofdm_demap_frames): segment s = seg_len symbols at sym + s*seg_stride, each with its own sigma.
+// A segment is cut into slices of SEG_SLICE symbols (the last one shorter); pass 1 writes one double per (segment, slice),
+// pass 2 adds a segment's partials in a fixed order.  The geometry depends on seg_len only, so a segment's outputs do not depend
+// on the batch it is in, on the grid or on the stream.
+constexpr int SEG_SLICE = 2048;
+inline int64_t seg_slices(int64_t seg_len) { return (seg_len + SEG_SLICE - 1) / SEG_SLICE; }
+enum : int { SEG_OUT_SOFT0 = 1, SEG_OUT_SOFT1 = 2, SEG_OUT_LLR = 4 };
+struct SegDemapArgs {
+    const cf* sym;
+    int64_t n_seg, seg_len, seg_stride;   // symbols
+    int64_t n_slices;        // seg_slices(seg_len)
+    int mod;                 // 2, 4, 6
+    float* soft0;            // [n_seg][seg_len*mod] llrp0, or null
+    float* soft1;            // [n_seg][seg_len*mod] llrp1, or null
+    float* llr;              // [n_seg][seg_len*mod] soft0 - soft1, or null
+    double* sigma;           // [n_seg], or null
+    double* partial;         // [n_seg][n_slices] workspace
+};
+
 // ---- TX (reference: MultiAntennaSystem.py:113-218) ---------------------------------------------
 struct TxDev {
     int nfft, cp, L, Ks, Kd, S, D, bps;
@@ -170,6 +189,8 @@ hipError_t launch_fo_finalize(const RxDev& rx, const SyncArgs& a, int units_per_
 // htime[r] = ifft(H[r]) for n_rows rows of nfft bins (est_chan_time on demand)
 hipError_t launch_rx_chan_time(const RxDev& rx, const cf* H, cf* htime, int n_rows, hipStream_t s);
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);
+// segmented soft de-mapper: pass 1 (nearest-point distance sums per slice) and pass 2 (sigma per segment + requested arrays)
+hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s);
 hipError_t launch_bit_errors(const uint8_t* a, const uint8_t* b, int64_t n, unsigned long long* count, hipStream_t s);
 // out[row][i] = mean_SF( in[row][SF + i*dsss] * conj(code[SF]) ), i < n_spread  (SynchEstFOAndDSSS.py:391-399)
 // rows visited in order; row r of frame f = f*D + n is divided by sqrt(mean |row f|^2) (SynchronizeAndEstimate.py:431-434)

@@ -1502,6 +1502,209 @@ __global__ void __launch_bounds__(256) demap_soft_qam64_kernel(DemapArgs a) {
     }
 }
 
+// ---- segmented soft de-mapper (ofdm_demap_frames): the metrics above with one sigma per segment (one frame of the batch).
+// Work item w = (segment w / n_slices, slice w % n_slices), workgroups loop over the items with the grid as stride.  Nothing is
+// added atomically: pass 1 writes one double per item, pass 2 adds a segment's partials in a fixed order, so a segment's outputs
+// are the same bits alone, in any batch and on every call.
+
+// sum of a double over the workgroup (256 lanes): butterfly per wave, then the four wave sums in order.  Every lane gets the
+// total; `sh` must not be touched by another reduction until the caller's next barrier.
+__device__ __forceinline__ double seg_block_sum(double v, double (&sh)[4]) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// Pass 1: a thread takes groups of FOUR consecutive symbols (two 16 B non-temporal loads where the slice is 16-byte aligned,
+// else four 8 B loads) and adds their distances to its running double sum ONE BY ONE, in the same order on both paths: the
+// partial does not depend on the alignment of the segment.
+template <int MOD>
+__global__ void __launch_bounds__(256) demap_seg_dmin_kernel(SegDemapArgs a) {
+    __shared__ double sh[4];
+    const int64_t n_items = a.n_seg * a.n_slices;
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const int64_t s = w / a.n_slices, first = (w - s * a.n_slices) * SEG_SLICE;
+        const int len = int(min(int64_t(SEG_SLICE), a.seg_len - first));
+        const cf* p = a.sym + s * a.seg_stride + first;
+        const bool wide = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < SEG_SLICE / 1024; ++k) {
+            const int i0 = 4 * (k * 256 + int(threadIdx.x));
+            if (i0 >= len) break;
+            cf z[4];
+            if (wide && i0 + 4 <= len) {
+                const float4 v0 = load_stream16(reinterpret_cast<const float*>(p + i0)),
+                             v1 = load_stream16(reinterpret_cast<const float*>(p + i0) + 4);
+                z[0] = cf{v0.x, v0.y};
+                z[1] = cf{v0.z, v0.w};
+                z[2] = cf{v1.x, v1.y};
+                z[3] = cf{v1.z, v1.w};
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) z[e] = i0 + e < len ? p[i0 + e] : cf{0.f, 0.f};
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (i0 + e < len) acc += double(demap_dmin<MOD>(z[e]));
+        }
+        const double tot = seg_block_sum(acc, sh);
+        if (threadIdx.x == 0) a.partial[w] = tot;
+        __syncthreads();
+    }
+}
+
+// per-symbol metrics of the segmented pass 2: llrp0 / llrp1 exactly as demap_soft_kernel (QPSK) / demap_soft_qam_kernel
+// (no products here are contracted, so that llr = llrp0 - llrp1 is the difference of the two stored values)
+template <int MOD>
+__device__ __forceinline__ void seg_metrics(cf z, float hf, float (&o0)[MOD], float (&o1)[MOD]) {
+#pragma clang fp contract(off)
+    if constexpr (MOD == 2) {
+        constexpr float K = 1.414213562373095f;
+        bool rp, ip;
+        cf e;
+        qpsk_nearest(z, rp, ip, e);
+        const float nr = hf * fabsf(e.x), fr = hf * (K - fabsf(e.x));
+        const float ni = hf * fabsf(e.y), fi = hf * (K - fabsf(e.y));
+        o0[0] = rp ? nr : fr;
+        o0[1] = ip ? ni : fi;
+        o1[0] = rp ? fr : nr;
+        o1[1] = ip ? fi : ni;
+    } else {
+        constexpr int NB = Pam<MOD>::NB;
+        float r0[NB], r1[NB], i0[NB], i1[NB], e;
+        Pam<MOD>::dist(z.x, r0, r1, e);
+        Pam<MOD>::dist(z.y, i0, i1, e);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            o0[2 * j] = hf * r0[j];
+            o0[2 * j + 1] = hf * i0[j];
+            o1[2 * j] = hf * r1[j];
+            o1[2 * j + 1] = hf * i1[j];
+        }
+    }
+}
+
+// Pass 2: sigma of the item's segment from its partials (each lane adds partials lane, lane+256, ... in order, then
+// seg_block_sum), hf = -0.5/sigma^2 as ofdm_demap, then the slice's requested arrays (OUTS = SEG_OUT_* bits; OUTS == 0: sigma
+// only, one item per segment).  llr = llrp0 - llrp1 of the two rounded values: the pragma keeps the compiler from contracting
+// hf*d0 - hf*d1 into an fma.  QPSK: two symbols per lane (16 B load, 16 B store per array); 16-QAM: one symbol per lane (8 B
+// load, 16 B store per array); 64-QAM: a wave's tile of 128 symbols through LDS as demap_soft_qam64_kernel, one array after
+// the other, so every store instruction writes 1 KB contiguous.  Slices that are not 16-byte aligned in the input or in a
+// requested output, and the symbols past the last full pair / tile, take per-float stores of the same values.
+template <int MOD, int OUTS>
+__global__ void __launch_bounds__(256) demap_seg_soft_kernel(SegDemapArgs a) {
+#pragma clang fp contract(off)
+    constexpr int TILE = 128;
+    constexpr bool S0 = (OUTS & SEG_OUT_SOFT0) != 0, S1 = (OUTS & SEG_OUT_SOFT1) != 0, LL = (OUTS & SEG_OUT_LLR) != 0;
+    __shared__ double sh[4];
+    __shared__ __attribute__((aligned(16))) float stage[MOD == 6 ? 4 : 1][MOD == 6 ? TILE * MOD : 4];
+    const int64_t per_seg = OUTS ? a.n_slices : 1;
+    const int64_t n_items = a.n_seg * per_seg;
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const int64_t s = w / per_seg, sl = w - s * per_seg;
+        const double* part = a.partial + s * a.n_slices;
+        double acc = 0.0;
+        for (int64_t i = threadIdx.x; i < a.n_slices; i += 256) acc += part[i];
+        const double sigma = 0.7071067811865476 * (seg_block_sum(acc, sh) / double(a.seg_len));
+        const float hf = float(-0.5 / (sigma * sigma));
+        if (sl == 0 && threadIdx.x == 0 && a.sigma) a.sigma[s] = sigma;
+        if constexpr (OUTS != 0) {
+            const int64_t first = sl * SEG_SLICE;
+            const int len = int(min(int64_t(SEG_SLICE), a.seg_len - first));
+            const cf* p = a.sym + s * a.seg_stride + first;
+            const int64_t obase = (s * a.seg_len + first) * MOD;                        // float index of the slice's outputs
+            float* q0 = S0 ? a.soft0 + obase : nullptr;
+            float* q1 = S1 ? a.soft1 + obase : nullptr;
+            float* ql = LL ? a.llr + obase : nullptr;
+            const bool wide = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q0) | reinterpret_cast<uintptr_t>(q1) |
+                                reinterpret_cast<uintptr_t>(ql)) & 15) == 0;
+            auto put1 = [&](int i, const float (&o0)[MOD], const float (&o1)[MOD]) {                  // symbol i, per float
+#pragma unroll
+                for (int b = 0; b < MOD; ++b) {
+                    if constexpr (S0) q0[int64_t(i) * MOD + b] = o0[b];
+                    if constexpr (S1) q1[int64_t(i) * MOD + b] = o1[b];
+                    if constexpr (LL) ql[int64_t(i) * MOD + b] = o0[b] - o1[b];
+                }
+            };
+            int done = 0;                                                                 // symbols handled by the wide path
+            if constexpr (MOD == 2) {
+                if (wide) {
+                    done = len & ~1;
+                    for (int g = threadIdx.x; 2 * g < done; g += 256) {
+                        const float4 v = load_stream16(reinterpret_cast<const float*>(p + 2 * g));
+                        float a0[2], a1[2], b0[2], b1[2];
+                        seg_metrics<2>(cf{v.x, v.y}, hf, a0, a1);
+                        seg_metrics<2>(cf{v.z, v.w}, hf, b0, b1);
+                        if constexpr (S0) store_stream16(q0 + 4 * g, float4{a0[0], a0[1], b0[0], b0[1]});
+                        if constexpr (S1) store_stream16(q1 + 4 * g, float4{a1[0], a1[1], b1[0], b1[1]});
+                        if constexpr (LL) store_stream16(ql + 4 * g, float4{a0[0] - a1[0], a0[1] - a1[1], b0[0] - b1[0], b0[1] - b1[1]});
+                    }
+                }
+            } else if constexpr (MOD == 4) {
+                if (wide) {
+                    done = len;
+                    typedef float f2 __attribute__((ext_vector_type(2)));
+                    for (int i = threadIdx.x; i < len; i += 256) {
+                        const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p + i));
+                        float o0[4], o1[4];
+                        seg_metrics<4>(cf{v.x, v.y}, hf, o0, o1);
+                        if constexpr (S0) store_stream16(q0 + 4 * i, float4{o0[0], o0[1], o0[2], o0[3]});
+                        if constexpr (S1) store_stream16(q1 + 4 * i, float4{o1[0], o1[1], o1[2], o1[3]});
+                        if constexpr (LL) store_stream16(ql + 4 * i, float4{o0[0] - o1[0], o0[1] - o1[1], o0[2] - o1[2], o0[3] - o1[3]});
+                    }
+                }
+            } else {
+                if (wide) {
+                    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+                    const int n_tiles = len / TILE;
+                    done = n_tiles * TILE;
+                    float* st = stage[wave];
+                    for (int t = wave; t < n_tiles; t += 4) {
+                        const float4 v = load_stream16(reinterpret_cast<const float*>(p + t * TILE + 2 * lane));
+                        float p0[6], p1[6], r0[6], r1[6];
+                        seg_metrics<6>(cf{v.x, v.y}, hf, p0, p1);                             // symbol 2*lane of the tile
+                        seg_metrics<6>(cf{v.z, v.w}, hf, r0, r1);                             // symbol 2*lane + 1
+                        // one array at a time through the wave's 3 KB: 12 floats per lane in, 3 x 16 B per lane out
+                        auto emit = [&](float* out, const float (&x)[6], const float (&y)[6]) {
+                            float4* wr = reinterpret_cast<float4*>(st + lane * 12);
+                            wr[0] = float4{x[0], x[1], x[2], x[3]};
+                            wr[1] = float4{x[4], x[5], y[0], y[1]};
+                            wr[2] = float4{y[2], y[3], y[4], y[5]};
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // wave-local exchange: in order per wave
+#pragma unroll
+                            for (int k = 0; k < 3; ++k) {
+                                const int piece = k * 64 + lane;
+                                store_stream16(out + int64_t(t) * (TILE * 6) + 4 * piece, *reinterpret_cast<const float4*>(st + 4 * piece));
+                            }
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // reads done before the stage is rewritten
+                        };
+                        if constexpr (S0) emit(q0, p0, r0);
+                        if constexpr (S1) emit(q1, p1, r1);
+                        if constexpr (LL) {
+                            float dp[6], dr[6];
+#pragma unroll
+                            for (int b = 0; b < 6; ++b) {
+                                dp[b] = p0[b] - p1[b];
+                                dr[b] = r0[b] - r1[b];
+                            }
+                            emit(ql, dp, dr);
+                        }
+                    }
+                }
+            }
+            for (int i = done + int(threadIdx.x); i < len; i += 256) {
+                float o0[MOD], o1[MOD];
+                seg_metrics<MOD>(p[i], hf, o0, o1);
+                put1(i, o0, o1);
+            }
+        }
+        __syncthreads();                                                                  // sh is reused by the next item
+    }
+}
+
 // ------------------------------------------------------------------------------------------ row renormalisation
 // SynchronizeAndEstimate.py:431-434: after row r = f*D + n has been equalised it is divided by sqrt(mean |row f|^2) -- row f,
 // not row r -- in loop order, so row f already carries its own final scaling (f <= r; f == r only for row 0).
@@ -1811,6 +2014,32 @@ hipError_t launch_demap(const DemapArgs& a, hipStream_t s) {
             hipLaunchKernelGGL(demap_soft_qam_kernel<4>, dim3(grid), dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL(demap_soft_qam64_kernel, dim3(unsigned(std::min<int64_t>(a.n / 512 + 1, OFDM_DEMAP_CAP2))), dim3(256), 0, s, a);
+    }
+    return hipGetLastError();
+}
+
+// Two launches, no memset: pass 1 writes every partial it covers.  The caller has checked the arguments and sized a.partial.
+template <int MOD>
+static void launch_demap_frames_mod(const SegDemapArgs& a, int outs, hipStream_t s) {
+    const int64_t items = a.n_seg * a.n_slices;
+    hipLaunchKernelGGL(demap_seg_dmin_kernel<MOD>, dim3(unsigned(std::min<int64_t>(items, OFDM_DEMAP_CAP1))), dim3(256), 0, s, a);
+    const unsigned g2 = unsigned(std::min<int64_t>(outs ? items : a.n_seg, OFDM_DEMAP_CAP2));
+    switch (outs) {
+#define OFDM_SEG(O) \
+    case O: hipLaunchKernelGGL((demap_seg_soft_kernel<MOD, O>), dim3(g2), dim3(256), 0, s, a); break;
+        OFDM_SEG(0) OFDM_SEG(1) OFDM_SEG(2) OFDM_SEG(3) OFDM_SEG(4) OFDM_SEG(5) OFDM_SEG(6) OFDM_SEG(7)
+#undef OFDM_SEG
+    }
+}
+hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s) {
+    if (a.n_seg <= 0 || a.seg_len <= 0) return hipSuccess;
+    const int outs = (a.soft0 ? SEG_OUT_SOFT0 : 0) | (a.soft1 ? SEG_OUT_SOFT1 : 0) | (a.llr ? SEG_OUT_LLR : 0);
+    if (!outs && !a.sigma) return hipSuccess;
+    switch (a.mod) {
+        case 2: launch_demap_frames_mod<2>(a, outs, s); break;
+        case 4: launch_demap_frames_mod<4>(a, outs, s); break;
+        case 6: launch_demap_frames_mod<6>(a, outs, s); break;
+        default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

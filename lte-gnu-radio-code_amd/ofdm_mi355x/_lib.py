@@ -70,6 +70,11 @@ class FoBatchOut(C.Structure):
                 ("chan_time", C.c_void_p), ("synch_freq", C.c_void_p)]
 
 
+class SoftOut(C.Structure):
+    """ofdm_soft_out: device pointers of the segmented soft de-mapper (None = not wanted)."""
+    _fields_ = [("soft0", C.c_void_p), ("soft1", C.c_void_p), ("llr", C.c_void_p), ("sigma", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -104,6 +109,11 @@ PROTOTYPES = {
     "ofdm_rx_set_max_trials": (C.c_int, [C.c_void_p, C.c_int32]),
     "ofdm_rx_set_sync_search": (C.c_int, [C.c_void_p, C.c_int32]),
     "ofdm_demap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ofdm_rx_reserve_soft": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "ofdm_demap_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.POINTER(SoftOut),
+                                    C.c_void_p]),
+    "ofdm_rx_demod_frames_soft": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.POINTER(SoftOut), C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

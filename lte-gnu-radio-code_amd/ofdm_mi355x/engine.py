@@ -159,6 +159,35 @@ class RxEngine:
         check(self.lib.ofdm_demap(self._h, ptr(d_sym), int(n), _mod_bits(modulation), ptr(d_hard), ptr(d_soft0),
                                   ptr(d_soft1), ptr(stream)))
 
+    # ---- segmented soft de-mapper: one sigma per segment (per frame of a batch) ----------------------------------
+    @staticmethod
+    def _soft_out(d_soft0, d_soft1, d_llr, d_sigma):
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        return _lib.SoftOut(addr(d_soft0), addr(d_soft1), addr(d_llr), addr(d_sigma))
+
+    def reserve_soft(self, n_seg: int, seg_len: int):
+        """Workspace of demap_frames / demod_frames_soft for n_seg segments of seg_len symbols (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_soft(self._h, int(n_seg), int(seg_len)))
+
+    def demap_frames(self, d_sym, n_seg, seg_len, seg_stride, modulation, d_soft0=None, d_soft1=None, d_llr=None, d_sigma=None,
+                     stream=None):
+        """ofdm_demap_frames: segment s = seg_len complex64 symbols at d_sym + s*seg_stride, each de-mapped as ofdm_demap would
+        de-map it alone.  Outputs [n_seg][seg_len*bps] float32 soft0 / soft1 / llr = soft0 - soft1, sigma [n_seg] float64."""
+        out = self._soft_out(d_soft0, d_soft1, d_llr, d_sigma)
+        check(self.lib.ofdm_demap_frames(self._h, ptr(d_sym), int(n_seg), int(seg_len), int(seg_stride), _mod_bits(modulation),
+                                         C.byref(out), ptr(stream)))
+
+    def demod_frames_soft(self, d_iq, n_frames, frame_stride, frame_len, d_eq, d_soft0=None, d_soft1=None, d_llr=None,
+                          d_sigma=None, d_bits=None, bits_mode=BITS_NONE, d_tsr=None, stream=None) -> int:
+        """demod_frames, then demap_frames over d_eq with one segment per frame (n_dsym*Kd symbols, the handle's modulation).
+        Returns n_dsym."""
+        out = self._soft_out(d_soft0, d_soft1, d_llr, d_sigma)
+        return int(check(self.lib.ofdm_rx_demod_frames_soft(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
+                                                            int(frame_len), ptr(d_eq), ptr(d_bits), int(bits_mode),
+                                                            ptr(d_tsr), C.byref(out), ptr(stream))))
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.lib.ofdm_rx_destroy(self._h)
