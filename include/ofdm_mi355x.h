@@ -182,6 +182,55 @@ int64_t ofdm_rx_demod_frames_soft(ofdm_rx* h, const float* d_iq, int64_t n_frame
                                   int64_t frame_len, float* d_eq, uint8_t* d_bits, int32_t bits_mode,
                                   int32_t* d_tsr, const ofdm_soft_out* soft, void* stream);
 
+/* ------------------------------------------------------------------------------------------ pilot-aided phase tracking
+ * The receive side of ofdm_tx_set_pilots / txOFDM.OFDM_Modulation(fft_size, pilot_locations): an extension, the reference's
+ * receivers have no pilot handling.  Convention: the handle's cfg.num_data_bins is the number of OCCUPIED bins K (= the
+ * transmitter's num_data_bins + n_pilots), so ofdm_rx_demod_frames runs exactly as without pilots and writes rows z[0..K) in the
+ * list order of binsP(K).  Pilots are n_pilots distinct signed bin offsets inside [-K/2..-1, 1..K/2] carrying pilot_re + j
+ * pilot_im (the rules of ofdm_tx_set_pilots); Kd' = K - n_pilots data entries remain per row, in list order.
+ * For one row, P = the pilots' list indices in ascending order, d_j = the j-th non-pilot list index:
+ *   U    = sum_{p in P} z[p] * conj(pilot_value), ascending p, float32
+ *   c    = conj(U)/|U| if |U|^2 is finite and > 0, else 1 (zero rows of guard-failed patterns and of frames without a sync
+ *          stay zero)
+ *   data[j] = c * z[d_j]                                   cpe[row] = U/|U| (the measured rotation), 0 for a row without usable U
+ *   bits = the hard decision (ofdm_demap's rules) of the STORED float32 data[j], cfg.modulation 2 / 4 / 6 bits per symbol
+ * OFDM_PILOT_CPE_SLOPE also removes a phase that is linear in the bin offset k: theta_p = arg(z[p] conj(pilot_value) c),
+ *   tau = sum (k_p - kbar) theta_p / sum (k_p - kbar)^2, delta = mean theta - tau kbar,
+ *   data[j] = c e^{-j(delta + tau k_{d_j})} z[d_j], slope[row] = tau (radians per bin; 0 for a row without usable U).
+ * Per segment: cfo = arg(sum U[s+1] conj(U[s])) / (2 pi L/N) in subcarrier spacings, over consecutive rows s, s+1 of the SAME
+ * pattern (they are L = nfft + cp samples apart; rows_per_pattern rows form a pattern), float64 sums, rows without usable U
+ * skipped; NaN if no pair exists.  Unambiguous for |cfo| < N/(2L).
+ * Deterministic: every sum has an order fixed by the row / the segment's geometry (no atomics), so a segment's outputs are the
+ * same bits alone, in any batch, at any alignment and on every call. */
+typedef enum { OFDM_PILOT_CPE = 0, OFDM_PILOT_CPE_SLOPE = 1 } ofdm_pilot_mode;
+/* Host array, copied into a small device table; n_pilots == 0 clears it.  Synchronises the device. */
+int ofdm_rx_set_pilots(ofdm_rx* h, const int32_t* h_locations, int32_t n_pilots, float pilot_re, float pilot_im);
+typedef struct ofdm_pilot_out {   /* DEVICE pointers; NULL = not wanted */
+    float*   data;       /* [n_seg][rows][Kd'] complex64; required with bits (and by the soft stage)              */
+    uint8_t* bits;       /* hard bits of data: packed MSB-first [n_seg][rows][Kd'*bps/8] or one bit per byte        */
+    int32_t  bits_mode;  /* ofdm_bits_mode of bits; OFDM_BITS_PACKED needs Kd'*bps % 8 == 0                         */
+    float*   cpe;        /* [n_seg][rows] complex64                                                                 */
+    float*   slope;      /* [n_seg][rows] float32, OFDM_PILOT_CPE_SLOPE only                                        */
+    double*  cfo;        /* [n_seg]                                                                                 */
+} ofdm_pilot_out;
+/* Device workspace for the cfo output of n_seg segments of `rows` rows (grows, never shrinks; synchronises the device).  Call it
+ * before capturing the two calls below into a hipGraph. */
+int ofdm_rx_reserve_pilots(ofdm_rx* h, int64_t n_seg, int64_t rows);
+/* The stage on any device buffer: segment s = `rows` rows of K complex64 symbols at d_sym + s*seg_stride (complex items;
+ * seg_stride >= rows*K), outputs dense per segment.  Asynchronous on `stream` (NULL = the handle's stream): one launch, plus a
+ * small one for cfo; no host synchronisation and no allocation once ofdm_rx_reserve_pilots covers the call.  Without pilots set,
+ * with mode CPE_SLOPE and fewer than two pilots, and for any other argument error: OFDM_ERR_INVALID before anything is enqueued.
+ * n_seg == 0 or an `out` without any pointer is a no-op returning OFDM_OK.  d_sym and the outputs must not overlap. */
+int ofdm_pilot_track_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t seg_stride,
+                            int32_t rows_per_pattern, int32_t mode, const ofdm_pilot_out* out, void* stream);
+/* ofdm_rx_demod_frames with the same arguments and d_bits = NULL (d_eq is required; d_eq and d_tsr get the bits of the plain
+ * call), then ofdm_pilot_track_frames over d_eq with one segment per frame (rows = n_dsym, rows_per_pattern = synch_D), then --
+ * if `soft` has a pointer -- ofdm_demap_frames over out->data with seg_len = seg_stride = n_dsym*Kd', so that a frame's sigma
+ * and LLRs are those of its TRACKED data symbols.  Returns n_dsym. */
+int64_t ofdm_rx_demod_frames_pilots(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride,
+                                    int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t mode,
+                                    const ofdm_pilot_out* out, const ofdm_soft_out* soft, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

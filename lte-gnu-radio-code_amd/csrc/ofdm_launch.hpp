@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <vector>
 #include "ofdm_device.hpp"
 
@@ -129,6 +130,39 @@ struct SegDemapArgs {
     double* partial;         // [n_seg][n_slices] workspace
 };
 
+// ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
+// Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
+// consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.
+struct PilotArgs {
+    const cf* sym;
+    int64_t n_seg, rows, seg_stride;      // segment s = rows rows of K symbols at sym + s*seg_stride (complex items)
+    int K, Kd, n_pilots;
+    int g_log2, rows_per_group;
+    int slope;               // OFDM_PILOT_CPE_SLOPE
+    int mod;                 // 2, 4, 6 (only read when bits != null)
+    cf pilot_conj;           // conj(pilot_value)
+    const int* pidx;         // [n_pilots] ascending list indices of the pilots
+    const float* pk;         // [n_pilots] their signed bin offsets
+    const uint16_t* src;     // [Kd rounded up to even] list index of the j-th data entry
+    float kbar, inv_skk;     // mean pilot offset, 1 / sum (k_p - kbar)^2
+    cf* data;                // [n_seg][rows][Kd], or null
+    uint8_t* bits;           // hard bits of data, or null
+    int bits_mode;
+    cf* cpe;                 // [n_seg][rows], or null
+    float* slope_out;        // [n_seg][rows], or null
+    cf* usum;                // [n_seg][rows] workspace: the pilot sum U of a usable row, else 0 (null: cfo not wanted)
+    double* cfo;             // [n_seg], or null
+    int rows_per_pattern;
+    double cfo_scale;        // nfft / (2 pi L)
+};
+inline int pilot_group_log2(int Kd) {
+    int g = 1;
+    while (g < 6 && (1 << g) < (Kd + 1) / 2) ++g;
+    return g;
+}
+// rows a lane group walks: about 4 KB of input per wave
+inline int pilot_rows_per_group(int K, int g_log2) { return std::max(1, 4096 / (K * 8 * (64 >> g_log2))); }
+
 // ---- TX (reference: MultiAntennaSystem.py:113-218) ---------------------------------------------
 struct TxDev {
     int nfft, cp, L, Ks, Kd, S, D, bps;
@@ -191,6 +225,8 @@ hipError_t launch_rx_chan_time(const RxDev& rx, const cf* H, cf* htime, int n_ro
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);
 // segmented soft de-mapper: pass 1 (nearest-point distance sums per slice) and pass 2 (sigma per segment + requested arrays)
 hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s);
+// pilot tracking stage: the row kernel, then (a.cfo != null) the per-segment offset estimate over a.usum
+hipError_t launch_pilot_track(const PilotArgs& a, hipStream_t s);
 hipError_t launch_bit_errors(const uint8_t* a, const uint8_t* b, int64_t n, unsigned long long* count, hipStream_t s);
 // out[row][i] = mean_SF( in[row][SF + i*dsss] * conj(code[SF]) ), i < n_spread  (SynchEstFOAndDSSS.py:391-399)
 // rows visited in order; row r of frame f = f*D + n is divided by sqrt(mean |row f|^2) (SynchronizeAndEstimate.py:431-434)

@@ -22,6 +22,7 @@ OFDM_ERR_UNBOUND = -6
 COMPAT_UTSA = 0
 COMPAT_RXOFDM = 1
 BITS_NONE, BITS_PACKED, BITS_UNPACKED = 0, 1, 2
+PILOT_CPE, PILOT_CPE_SLOPE = 0, 1
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -75,6 +76,12 @@ class SoftOut(C.Structure):
     _fields_ = [("soft0", C.c_void_p), ("soft1", C.c_void_p), ("llr", C.c_void_p), ("sigma", C.c_void_p)]
 
 
+class PilotOut(C.Structure):
+    """ofdm_pilot_out: device pointers of the pilot tracking stage (None = not wanted)."""
+    _fields_ = [("data", C.c_void_p), ("bits", C.c_void_p), ("bits_mode", C.c_int32), ("cpe", C.c_void_p), ("slope", C.c_void_p),
+                ("cfo", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -114,6 +121,12 @@ PROTOTYPES = {
                                     C.c_void_p]),
     "ofdm_rx_demod_frames_soft": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.c_void_p, C.POINTER(SoftOut), C.c_void_p]),
+    "ofdm_rx_set_pilots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float]),
+    "ofdm_rx_reserve_pilots": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "ofdm_pilot_track_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                          C.POINTER(PilotOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_pilots": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_int32, C.POINTER(PilotOut), C.POINTER(SoftOut), C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

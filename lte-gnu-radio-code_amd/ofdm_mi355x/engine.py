@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BITS_NONE, BITS_PACKED, BITS_UNPACKED, MODULATION_BITS, check, ptr
+from ._lib import BITS_NONE, BITS_PACKED, BITS_UNPACKED, MODULATION_BITS, PILOT_CPE, check, ptr
 
 
 def bins_p(num_bins: int, nfft: int) -> np.ndarray:
@@ -187,6 +187,44 @@ class RxEngine:
         return int(check(self.lib.ofdm_rx_demod_frames_soft(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
                                                             int(frame_len), ptr(d_eq), ptr(d_bits), int(bits_mode),
                                                             ptr(d_tsr), C.byref(out), ptr(stream))))
+
+    # ---- pilot-aided phase tracking: cfg.num_data_bins = occupied bins K, Kd' = K - n_pilots data entries per row ---------
+    def set_pilots(self, locations, value=1.0 + 0.0j):
+        """Signed bin offsets of the pilots (e.g. -21, -7, 7, 21) and their value, as TxEngine.set_pilots; () clears them."""
+        loc = np.ascontiguousarray(list(locations), dtype=np.int32)
+        check(self.lib.ofdm_rx_set_pilots(self._h, ptr(loc) if loc.size else None, int(loc.size), float(np.real(value)),
+                                          float(np.imag(value))))
+        self.n_pilots = int(loc.size)
+
+    @staticmethod
+    def _pilot_out(d_data, d_bits, bits_mode, d_cpe, d_slope, d_cfo):
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        return _lib.PilotOut(addr(d_data), addr(d_bits), int(bits_mode), addr(d_cpe), addr(d_slope), addr(d_cfo))
+
+    def reserve_pilots(self, n_seg: int, rows: int):
+        """Workspace of the cfo output for n_seg segments of `rows` rows (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_pilots(self._h, int(n_seg), int(rows)))
+
+    def pilot_track_frames(self, d_sym, n_seg, rows, seg_stride, rows_per_pattern, mode=PILOT_CPE, d_data=None, d_bits=None,
+                           bits_mode=BITS_NONE, d_cpe=None, d_slope=None, d_cfo=None, stream=None):
+        """ofdm_pilot_track_frames: segment s = `rows` rows of K complex64 symbols at d_sym + s*seg_stride.  Outputs per segment:
+        data [rows][Kd'] complex64, its hard bits, cpe [rows] complex64, slope [rows] float32, cfo float64."""
+        out = self._pilot_out(d_data, d_bits, bits_mode, d_cpe, d_slope, d_cfo)
+        check(self.lib.ofdm_pilot_track_frames(self._h, ptr(d_sym), int(n_seg), int(rows), int(seg_stride), int(rows_per_pattern),
+                                               int(mode), C.byref(out), ptr(stream)))
+
+    def demod_frames_pilots(self, d_iq, n_frames, frame_stride, frame_len, d_eq, mode=PILOT_CPE, d_data=None, d_bits=None,
+                            bits_mode=BITS_NONE, d_cpe=None, d_slope=None, d_cfo=None, d_soft0=None, d_soft1=None, d_llr=None,
+                            d_sigma=None, d_tsr=None, stream=None) -> int:
+        """demod_frames (d_eq: rows of K symbols), the pilot stage over d_eq with one segment per frame, then demap_frames over
+        d_data (n_dsym*Kd' symbols per frame) if a soft output is given.  Returns n_dsym."""
+        out = self._pilot_out(d_data, d_bits, bits_mode, d_cpe, d_slope, d_cfo)
+        soft = self._soft_out(d_soft0, d_soft1, d_llr, d_sigma)
+        return int(check(self.lib.ofdm_rx_demod_frames_pilots(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
+                                                              int(frame_len), ptr(d_eq), ptr(d_tsr), int(mode), C.byref(out),
+                                                              C.byref(soft), ptr(stream))))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
