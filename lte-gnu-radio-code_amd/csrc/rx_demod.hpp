@@ -354,6 +354,9 @@ struct DemodGeom {
     static constexpr int Q_OFF = W1_OFF + WgLds<N>::W1_ELEMS;               // 2 cf: the work-queue slot
     static constexpr int G_OFF = Q_OFF + 2;
     static size_t lds_bytes(int Kd, bool glds) { return (size_t(G_OFF) + (glds ? ((Kd + 3) & ~3) : 0)) * sizeof(cf); }
+    // The bin-list length the dense path (N >= 1024) is also compiled for: the LTE numerologies 1024/600, 2048/1200, 4096/2400.
+    // Any other Kd runs the runtime-Kd kernel (rx_demod_kernel's KD = 0).
+    static constexpr int KD_LTE = (N >= 1024) ? N * 75 / 128 : 0;
 };
 
 // Kernel build flags.  The product library instantiates FLAGS = 0 (batch and stream paths), DF_ROT (CFO receiver) and DF_HG
@@ -378,8 +381,15 @@ enum DemodFlags : unsigned {
                                  // stores 32 B apart: every store instruction of a wave covers 2 KB half-filled)
 };
 
-template <int N, int MOD, int BMODE, int MINW, unsigned FLAGS = 0>
+// KD    0: the bin-list length is the runtime rx.Kd.  > 0: it is this constant (the host launches such an instantiation only
+//       when rx.Kd == KD).  Kd belongs to the numerology, not to the call: with it fixed, every decision the symbol loop derives
+//       from it -- the class of each register slot (unlisted / listed / mixed), which 128-entry output blocks lie inside the
+//       list, off_neg / off_pos, the Kd == N case -- is a constant once the loops are unrolled.  With a runtime Kd hipcc hoists
+//       those decisions out of the symbol loop as 64-bit masks, spills them (124-185 SGPRs at >= 1024-pt) and re-reads them with
+//       ~118 v_readlane per wave and symbol (profiles/demod_resources.txt has both sides).
+template <int N, int MOD, int BMODE, int MINW, unsigned FLAGS = 0, int KD = 0>
 __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev rx, DemodArgs a) {
+    static_assert(KD >= 0 && KD <= N && KD % 4 == 0, "compile-time bin-list length");
     constexpr bool ROT = (FLAGS & DF_ROT) != 0, HG = (FLAGS & DF_HG) != 0, UNITS = (FLAGS & DF_UNITS) != 0,
                    GREG = (FLAGS & DF_GAINS_VGPR) != 0 && Plan<N>::T >= 64 && (FLAGS & DF_FOUR_PER_LANE) == 0 && !(MOD == 1 && BMODE == 1),
                    GLDS = (FLAGS & DF_GAINS_GLOBAL) == 0 && !GREG,
@@ -452,7 +462,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
     const int ds1 = min(int(int64_t(cidx + 1) * trips / a.chunks_per_frame) * NS, a.n_dsym);
     constexpr bool active = true;
 
-    const int Kd = rx.Kd, L = rx.L, S = rx.S, D = rx.D;
+    const int Kd = KD > 0 ? KD : rx.Kd, L = rx.L, S = rx.S, D = rx.D;
     const int tsr0 = a.tsr[frame * 4 + 0];
     const bool frame_on = (HG || UNITS) ? (a.tsr[frame * 4 + 3] != 0) : true;     // host-applied guard (tracker) / live unit
     const int src_frame = UNITS ? frame / a.units_per_frame : frame;
@@ -514,8 +524,11 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
                 for (int n0 = 0; n0 < P; ++n0) v[n0] = cmul(v[n0], rotp[t + T * n0]);
             }
         } else {                                                         // short tail: fft(x, N) zero-pads (:230)
-            const int64_t last = a.frame_len > 0 ? a.frame_len - 1 : 0;
-            const bool any = sy.compute && a.frame_len > 0;
+            // the window's valid elements are [lo, hi) of its N (both clamped to [0, N]): the lane arithmetic below is 32-bit
+            // (as 64-bit sample indices it held nine 64-bit constants in SGPR pairs across the symbol loop)
+            const int64_t before = -sy.start, left = a.frame_len - sy.start;
+            const int lo = int(before < 0 ? 0 : (before < N ? before : N)), hi = int(left < 0 ? 0 : (left < N ? left : N));
+            const bool any = sy.compute && hi > lo;
             // Rare path.  Its 16 clamped element addresses are loop-invariant up to the symbol offset, and hipcc hoists what it can
             // out of the symbol loop: 26 VGPRs held (or spilled) for the whole kernel.  The lane index therefore passes through an
             // opaque copy HERE, so everything below is computed where it is used.
@@ -523,9 +536,9 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
             asm volatile("" : "+v"(tq));
 #pragma unroll
             for (int n0 = 0; n0 < P; ++n0) {
-                const int64_t idx = sy.start + tq + T * n0;
-                const cf x = any ? frame_iq[idx < 0 ? 0 : (idx < last ? idx : last)] : cf{0.f, 0.f};
-                v[n0] = (any && idx >= 0 && idx < a.frame_len) ? x : cf{0.f, 0.f};
+                const int e = tq + T * n0;
+                const cf x = any ? frame_iq[sy.start + min(max(e, lo), hi - 1)] : cf{0.f, 0.f};      // clamped: a valid address
+                v[n0] = (any && e >= lo && e < hi) ? x : cf{0.f, 0.f};
                 if constexpr (ROT) v[n0] = cmul(v[n0], rotp[tq + T * n0]);
             }
         }
@@ -705,6 +718,9 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
             const cf* const l_lane = lds + lane_e;
             const cf* const g_lane = gsrc + lane_e;
             const unsigned eq_off = unsigned(lane_e) * unsigned(sizeof(cf));             // byte offset of the lane's pair within a row
+            // Compile-time Kd: the lane compares of the one straddling block are loop-invariant, and hoisted they are 64-bit masks
+            // that the allocator spills.  Through an opaque copy each is one v_cmp against a constant where it is used.
+            const int lnm = (KD > 0) ? opaque_lane(ln) : ln;
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
                 const int b0 = 4 * T * q + 256 * wv;                                      // scalar
@@ -752,7 +768,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
                         if (base + 128 <= Kd_) {                                          // scalar: the whole block is listed
                             pair();
                         } else if (base < Kd_) {                                          // scalar: the block that straddles Kd
-                            if (base + 2 * ln < Kd_) pair();
+                            if (base + 2 * lnm < Kd_) pair();
                         }
                     }
                     if constexpr (BMODE == 1) {
@@ -767,7 +783,7 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
                         uint8_t* const brow = bits_row + (4 * T * q / 4) * (MOD / 2);     // scalar
                         if (b0 + 256 <= Kd_) {
                             store_packed4<MOD>(brow, unsigned(ge), w4);
-                        } else if (4 * T * q + ge < Kd_) {
+                        } else if (4 * T * q + ((KD > 0) ? opaque_lane(ge) : ge) < Kd_) {
                             store_packed4<MOD>(brow, unsigned(ge), w4);
                         }
                     }
@@ -830,6 +846,75 @@ __global__ void __launch_bounds__(DemodGeom<N>::WG, MINW) rx_demod_kernel(RxDev 
         }
     }
 }
+
+// The FLAGS = 0 batch launch of one (N, KD): the no-bits kernel plus 4 mods x 2 bit modes.  KD = 0 is the runtime-Kd kernel, KD > 0
+// the instantiation with that bin-list length compiled in (the caller checked rx.Kd == KD).  Occupancy query, LDS announcement
+// and the work queue's grid all belong to the instantiation launched here: their statics are per (N, KD).
+template <int N, int KD>
+hipError_t launch_rx_demod_batch(const RxDev& rx, DemodArgs a, unsigned grid, size_t lds, int bmode, hipStream_t s) {
+    using DG = DemodGeom<N>;
+    constexpr int MW = (Plan<N>::T == 128) ? OFDM_MINW_T128 : 3;
+    constexpr unsigned FL = (Plan<N>::T == 128) ? OFDM_FLAGS_T128 : (Plan<N>::T == 256) ? OFDM_FLAGS_T256 : 0u;
+    // more than 64 KB of dynamic LDS per workgroup (4 slots at 2048-pt) has to be announced once per kernel
+#define OFDM_LD(M, B)                                                                                                        \
+    do {                                                                                                                     \
+        static std::atomic<int> announced{65536};          /* grows with Kd (gain table): announce every new maximum */      \
+        if (int(lds) > announced.load(std::memory_order_relaxed)) {                                                          \
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rx_demod_kernel<N, M, B, MW, FL, KD>),         \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));                       \
+            if (e != hipSuccess) return e;                                                                                   \
+            announced.store(int(lds), std::memory_order_relaxed);                                                            \
+        }                                                                                                                    \
+        hipLaunchKernelGGL((rx_demod_kernel<N, M, B, MW, FL, KD>), dim3(grid), dim3(DG::WG), lds, s, rx, a);                 \
+    } while (0)
+    // below 1024-pt a chunk is a whole frame or a large part of one and the static grid measured 1-5 % ahead of the queue
+    // (profiles/r03_small_sizes.txt)
+    if (N < 1024) a.work = nullptr;
+    if (a.work) {
+        // work queue: the resident workgroups only (occupancy of the 16-QAM packed instantiation of THIS KD stands for all of them:
+        // the register counts of the MOD / BMODE variants differ by a few VGPRs, and from 1024-pt up LDS is what bounds residency;
+        // the queue itself is correct with any grid size)
+        static int per_cu = 0, n_cu = 0;
+        if (per_cu == 0) {
+            int nb = 0, dev = 0;
+            hipDeviceProp_t prop;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rx_demod_kernel<N, 4, 1, MW, FL, KD>, DG::WG, lds) != hipSuccess || nb < 1) nb = 2;
+            n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                       ? prop.multiProcessorCount : 256;
+            per_cu = nb;
+        }
+        const int64_t resident = int64_t(per_cu) * n_cu;
+        if (int64_t(grid) > 2 * resident)
+            grid = unsigned(resident);
+        else
+            a.work = nullptr;                     // not worth a queue: one chunk per workgroup
+    }
+#define OFDM_LD_MOD(B)                  \
+    switch (a.mod) {                    \
+        case 1: OFDM_LD(1, B); break;   \
+        case 2: OFDM_LD(2, B); break;   \
+        case 4: OFDM_LD(4, B); break;   \
+        default: OFDM_LD(6, B); break;  \
+    }
+    if (bmode == 0) {
+        OFDM_LD(2, 0);
+    } else if (bmode == 1) {
+        OFDM_LD_MOD(1)
+    } else {
+        OFDM_LD_MOD(2)
+    }
+#undef OFDM_LD_MOD
+#undef OFDM_LD
+    return hipGetLastError();
+}
+
+// The compiled-in-Kd launches are instantiated in translation units of their own (rx_demod_<N>_kd.hip: the build stays parallel)
+#define OFDM_EXTERN_DEMOD_KD(n) \
+    extern template hipError_t launch_rx_demod_batch<n, DemodGeom<n>::KD_LTE>(const RxDev&, DemodArgs, unsigned, size_t, int, hipStream_t);
+OFDM_EXTERN_DEMOD_KD(1024)
+OFDM_EXTERN_DEMOD_KD(2048)
+OFDM_EXTERN_DEMOD_KD(4096)
+#undef OFDM_EXTERN_DEMOD_KD
 
 // one translation unit per FFT size instantiates this (rx_demod_<N>.hip)
 template <int N>
@@ -953,59 +1038,10 @@ hipError_t launch_rx_demod_n(const RxDev& rx, const DemodArgs& a_in, hipStream_t
         }
     }
 #endif
-    constexpr int MW = (Plan<N>::T == 128) ? OFDM_MINW_T128 : 3;
-    constexpr unsigned FL = (Plan<N>::T == 128) ? OFDM_FLAGS_T128 : (Plan<N>::T == 256) ? OFDM_FLAGS_T256 : 0u;
-    // more than 64 KB of dynamic LDS per workgroup (4 slots at 2048-pt) has to be announced once per kernel
-#define OFDM_LD(M, B)                                                                                                        \
-    do {                                                                                                                     \
-        static std::atomic<int> announced{65536};          /* grows with Kd (gain table): announce every new maximum */      \
-        if (int(lds) > announced.load(std::memory_order_relaxed)) {                                                          \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&rx_demod_kernel<N, M, B, MW, FL>),             \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));                       \
-            if (e != hipSuccess) return e;                                                                                   \
-            announced.store(int(lds), std::memory_order_relaxed);                                                            \
-        }                                                                                                                    \
-        hipLaunchKernelGGL((rx_demod_kernel<N, M, B, MW, FL>), dim3(grid), dim3(DG::WG), lds, s, rx, a);                     \
-    } while (0)
-    // below 1024-pt a chunk is a whole frame or a large part of one and the static grid measured 1-5 % ahead of the queue
-    // (profiles/r03_small_sizes.txt)
-    if (N < 1024) a.work = nullptr;
-    if (a.work) {
-        // work queue: the resident workgroups only (occupancy of the 16-QAM packed instantiation stands for all of them: the
-        // register counts of the MOD / BMODE variants differ by a few VGPRs inside one occupancy step; the queue itself is
-        // correct with any grid size)
-        static int per_cu = 0, n_cu = 0;
-        if (per_cu == 0) {
-            int nb = 0, dev = 0;
-            hipDeviceProp_t prop;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rx_demod_kernel<N, 4, 1, MW, FL>, DG::WG, lds) != hipSuccess || nb < 1) nb = 2;
-            n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                       ? prop.multiProcessorCount : 256;
-            per_cu = nb;
-        }
-        const int64_t resident = int64_t(per_cu) * n_cu;
-        if (int64_t(grid) > 2 * resident)
-            grid = unsigned(resident);
-        else
-            a.work = nullptr;                     // not worth a queue: one chunk per workgroup
+    if constexpr (DemodGeom<N>::KD_LTE > 0) {
+        if (rx.Kd == DemodGeom<N>::KD_LTE) return launch_rx_demod_batch<N, DemodGeom<N>::KD_LTE>(rx, a, grid, lds, bmode, s);
     }
-#define OFDM_LD_MOD(B)                  \
-    switch (a.mod) {                    \
-        case 1: OFDM_LD(1, B); break;   \
-        case 2: OFDM_LD(2, B); break;   \
-        case 4: OFDM_LD(4, B); break;   \
-        default: OFDM_LD(6, B); break;  \
-    }
-    if (bmode == 0) {
-        OFDM_LD(2, 0);
-    } else if (bmode == 1) {
-        OFDM_LD_MOD(1)
-    } else {
-        OFDM_LD_MOD(2)
-    }
-#undef OFDM_LD_MOD
-#undef OFDM_LD
-    return hipGetLastError();
+    return launch_rx_demod_batch<N, 0>(rx, a, grid, lds, bmode, s);
 }
 
 #define OFDM_DECLARE_DEMOD(n) hipError_t launch_rx_demod_##n(const RxDev& rx, const DemodArgs& a, hipStream_t s);
