@@ -292,6 +292,62 @@ int ofdm_channel_apply(ofdm_tx* h, const float* d_in, int64_t n_frames, int64_t 
                        const float* d_taps, int32_t n_taps, int32_t per_frame_taps, float noise_var,
                        uint64_t seed, float* d_out, int64_t out_stride, int64_t out_len, void* stream);
 
+/* ------------------------------------------------------------------------------------------ channel code (LTE TBCC)
+ * The tail-biting convolutional code of 3GPP TS 36.212 5.1.3.1 on the frame-batched path: an encoder in front of
+ * ofdm_tx_modulate_frames and a decoder behind the LLRs of ofdm_demap_frames / ofdm_rx_demod_frames_soft /
+ * ofdm_rx_demod_frames_pilots.  An extension: the reference has no channel code, so this text is the contract.  The sub-block
+ * interleaver and the circular-buffer rate matching of 5.1.4.2 are NOT part of it: the coded order is the plain interleaving
+ * below and the rate is always 1/3.
+ * Code block: K information bits c[0..K), K a multiple of 8 with 24 <= K <= 2048; indices are taken mod K (tail-biting: the
+ * register starts in the state of the last six bits).
+ * Encoder:  d0[k] = c[k]^c[k-2]^c[k-3]^c[k-5]^c[k-6]   (generator 133 octal)
+ *           d1[k] = c[k]^c[k-1]^c[k-2]^c[k-3]^c[k-6]   (171)
+ *           d2[k] = c[k]^c[k-1]^c[k-2]^c[k-4]^c[k-6]   (165)          e[3k+j] = dj[k]: 3K coded bits.
+ * Segments: a segment is one frame's bit stream of seg_bits bits (receiver: n_dsym*Kd*bps, with pilots n_dsym*Kd'*bps;
+ * transmitter: the n_data_sym*Kd*bps bits ofdm_tx_modulate_frames takes per frame).  It carries blocks_per_seg <=
+ * floor(seg_bits/(3K)) blocks back to back from bit 0; the encoder writes the rest of the segment as zeros (filler), the
+ * decoder ignores it.
+ * Decoder: wrap-around Viterbi, non-iterative, fully determined; all arithmetic IEEE float32 in the order written.
+ *   state s = sum_{i=1..6} c[k-i] 2^(6-i); input b takes s to s' = (b<<5)|(s>>1); the predecessors of s' are p0 = (s'<<1)&63 and
+ *   p1 = p0|1; output bit j of the transition p -> s' is parity((((s'>>5)<<6) | p) & Gj), G = 0133, 0171, 0165 (bit 6 = input).
+ *   An LLR that is not finite counts as 0; positive favours bit 0 (the convention of ofdm_soft_out.llr).
+ *   W = 96, T = K + 2W steps; step t uses the LLRs l0, l1, l2 of information index (t - W) mod K; all 64 start metrics are 0.
+ *   Per state s': bm = (sg0*l0 + sg1*l1) + sg2*l2, sgj = +1 where output bit j of the p0 branch is 0, -1 where it is 1 (the p1
+ *   branch has all three bits flipped -- every generator taps delay 6 -- so its metric is exactly -bm);
+ *   cand0 = pm[p0] + bm, cand1 = pm[p1] - bm, decision = (cand1 > cand0) (a tie takes p0), pm'[s'] = the chosen candidate.
+ *   No renormalisation: finite LLRs whose sums overflow float32 are outside the contract.
+ *   After step T-1 the end state is the one with the largest metric, the lowest index on a tie.  Traceback t = T-1 .. 0:
+ *   bit[t] = s_{t+1} >> 5, s_t = ((s_{t+1} << 1) & 63) | decision[t][s_{t+1}].
+ *   Outputs per block: the bits of steps W .. W+K-1; metric = the end state's path metric; tb_ok = 1 iff s_W == s_{W+K} (a
+ *   consistency diagnostic, not an error detector).
+ * Deterministic: a block's outputs depend on its own 3K LLRs only -- the same bits alone, in any batch, at any stride and on
+ * every call (no atomics). */
+/* floor(seg_bits / (3K)): the blocks a segment can carry.  Host arithmetic; OFDM_ERR_INVALID for a bad K or seg_bits < 0. */
+int64_t ofdm_tbcc_blocks(int64_t seg_bits, int32_t K);
+/* d_info: dense [n_seg][blocks_per_seg][K] information bits, d_coded: [n_seg][seg_bits] coded bits + filler; each side packed
+ * MSB-first or one bit per byte (ofdm_bits_mode; packed coded output needs seg_bits % 8 == 0).  Asynchronous on `stream`
+ * (NULL = the handle's stream), one launch, no allocation.  n_seg == 0 or seg_bits == 0 is a no-op; argument errors return
+ * OFDM_ERR_INVALID before anything is enqueued. */
+int ofdm_tx_tbcc_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                               int32_t K, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream);
+typedef struct ofdm_tbcc_out {   /* DEVICE pointers; NULL = not wanted */
+    uint8_t* bits;       /* dense [n_seg][blocks_per_seg][K] decoded bits: packed MSB-first (K/8 bytes per block) or one per byte */
+    int32_t  bits_mode;  /* ofdm_bits_mode of bits                                                                             */
+    float*   metric;     /* [n_seg][blocks_per_seg] float32                                                                    */
+    int32_t* tb_ok;      /* [n_seg][blocks_per_seg]                                                                            */
+} ofdm_tbcc_out;
+/* Prepares the handle's device for decoding up to n_blocks blocks of K bits per call: the decoder keeps its survivors in LDS and
+ * needs no device workspace, so this checks the geometry and loads the kernel.  Call it before capturing ofdm_tbcc_decode_frames
+ * into a hipGraph. */
+int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K);
+/* Block (s, b) reads the 3K float32 LLRs at d_llr + s*seg_stride + b*3K (seg_stride in floats, >= blocks_per_seg*3K), so the
+ * call works on any LLR buffer.  Asynchronous on `stream` (NULL = the handle's stream): one launch, no host synchronisation and
+ * no allocation.  n_seg == 0, blocks_per_seg == 0 or an `out` without any pointer is a no-op returning OFDM_OK.  Argument errors
+ * (NULL handle, bad K, seg_stride too short, a negative count, a batch beyond the kernel's index range) return OFDM_ERR_INVALID
+ * before anything is enqueued and without touching the device. */
+int ofdm_tbcc_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
+                            const ofdm_tbcc_out* out, void* stream);
+
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the
  * gr-RXOFDM receiver (root-37 ZC, stride cp-1, gate 0.4, linear SNR) plus a brute-force carrier

@@ -2180,6 +2180,96 @@ int ofdm_tx_create(const ofdm_tx_cfg* c, ofdm_tx** out) {
     return OFDM_OK;
 }
 
+// ---- LTE tail-biting convolutional code on the frame-batched path (definition: include/ofdm_mi355x.h)
+namespace {
+constexpr int64_t TBCC_MAX_BLOCKS = (int64_t(1) << 31) - 1;   // one workgroup per block: the grid's x range
+constexpr int64_t TBCC_MAX_ITEMS = int64_t(1) << 40;          // n_seg * seg_stride (floats) and n_seg * seg_bits
+bool tbcc_bits_mode_ok(int32_t m) { return m == OFDM_BITS_PACKED || m == OFDM_BITS_UNPACKED; }
+// argument check shared by reserve and decode (no device access); "" = fine
+const char* tbcc_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K) {
+    if (!tbcc_valid_k(K)) return "K must be a multiple of 8 with 24 <= K <= 2048";
+    if (n_seg < 0 || blocks_per_seg < 0) return "negative count";
+    if (blocks_per_seg > TBCC_MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS / blocks_per_seg))
+        return "batch beyond the kernels' index range";
+    return "";
+}
+}  // namespace
+
+int64_t ofdm_tbcc_blocks(int64_t seg_bits, int32_t K) {
+    if (!tbcc_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_blocks: K must be a multiple of 8 with 24 <= K <= 2048");
+    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_blocks: negative seg_bits");
+    return seg_bits / (3 * int64_t(K));
+}
+
+int ofdm_tx_tbcc_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                               int32_t K, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: null handle");
+    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: %s", bad);
+    if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode))
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+    if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * 3 * K)
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: seg_bits < blocks_per_seg * 3K");
+    if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7))
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: packed coded bits need seg_bits %% 8 == 0");
+    if (seg_bits > TBCC_MAX_ITEMS || (n_seg > 0 && seg_bits > TBCC_MAX_ITEMS / n_seg))
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: batch beyond the kernel's index range");
+    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
+    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: null buffer");
+    TbccEncArgs a{};
+    a.info = d_info;
+    a.info_mode = info_mode;
+    a.n_seg = n_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.coded = d_coded;
+    a.coded_mode = coded_mode;
+    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_tbcc_encode(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return OFDM_OK;
+}
+
+// The decoder keeps its survivors in LDS and has no device workspace, so there is nothing to allocate: the call checks the
+// geometry a later decode will use and loads the kernel's code object, which is the one piece of set-up a first launch would
+// otherwise do inside a capture.
+int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tbcc: null handle");
+    const char* bad = tbcc_bad_geometry(1, n_blocks, K);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tbcc: %s", bad);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(tbcc_decode_prepare());
+    return OFDM_OK;
+}
+
+int ofdm_tbcc_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
+                            const ofdm_tbcc_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: null handle");
+    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: %s", bad);
+    if (seg_stride < int64_t(blocks_per_seg) * 3 * K)
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: seg_stride < blocks_per_seg * 3K");
+    if (seg_stride > TBCC_MAX_ITEMS || (n_seg > 0 && seg_stride > TBCC_MAX_ITEMS / n_seg))
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: batch beyond the kernel's index range");
+    if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode))
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+    if (n_seg == 0 || blocks_per_seg == 0 || !out || (!out->bits && !out->metric && !out->tb_ok)) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: null d_llr");
+    TbccDecArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_seg * blocks_per_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.bits = out->bits;
+    a.bits_mode = out->bits_mode;
+    a.metric = out->metric;
+    a.tb_ok = out->tb_ok;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_tbcc_decode(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return OFDM_OK;
+}
+
 // ---- decomposed stages
 int ofdm_tx_random_bits(ofdm_tx* h, uint64_t seed, uint64_t offset, uint8_t* d_bits, int64_t n_bits, void* stream) {
     if (!h || (!d_bits && n_bits > 0) || n_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_tx_random_bits: bad argument");

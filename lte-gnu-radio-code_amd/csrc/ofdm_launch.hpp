@@ -213,6 +213,35 @@ struct ChanArgs {
     int64_t out_stride, out_len;
 };
 
+// ---- LTE tail-biting convolutional code (tbcc.hip; contract: include/ofdm_mi355x.h)
+constexpr int TBCC_W = 96;               // wrap-around depth: the decoder runs T = K + 2W trellis steps
+constexpr int TBCC_K_MIN = 24, TBCC_K_MAX = 2048;
+inline bool tbcc_valid_k(int64_t K) { return K >= TBCC_K_MIN && K <= TBCC_K_MAX && K % 8 == 0; }
+struct TbccEncArgs {
+    const uint8_t* info;     // dense [n_seg][blocks_per_seg][K] bits
+    int info_mode;           // ofdm_bits_mode
+    int64_t n_seg;
+    int blocks_per_seg, K;
+    uint8_t* coded;          // [n_seg][seg_bytes]: blocks_per_seg*3K coded bits from bit 0, then zeros
+    int coded_mode;          // ofdm_bits_mode
+    int64_t seg_bytes;       // seg_bits (one bit per byte) or seg_bits / 8 (packed)
+};
+struct TbccDecArgs {
+    const float* llr;        // block (seg, b) = 3K floats at llr + seg*seg_stride + b*3K
+    int64_t seg_stride;      // floats
+    int64_t n_blocks;        // n_seg * blocks_per_seg: one workgroup of one wave each
+    int blocks_per_seg, K;
+    uint8_t* bits;           // dense [n_blocks][K] bits, or null
+    int bits_mode;           // ofdm_bits_mode
+    float* metric;           // [n_blocks], or null
+    int32_t* tb_ok;          // [n_blocks], or null
+};
+hipError_t launch_tbcc_encode(const TbccEncArgs& a, hipStream_t s);
+hipError_t launch_tbcc_decode(const TbccDecArgs& a, hipStream_t s);
+// loads the decoder's code object (so that a first launch inside a stream capture has nothing left to set up)
+hipError_t tbcc_decode_prepare();
+size_t tbcc_lds_bytes(int K);            // survivor memory of one block: 8 B per trellis step, rounded up to 32 steps
+
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
 // batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs

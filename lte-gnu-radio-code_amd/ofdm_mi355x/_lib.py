@@ -82,6 +82,11 @@ class PilotOut(C.Structure):
                 ("cfo", C.c_void_p)]
 
 
+class TbccOut(C.Structure):
+    """ofdm_tbcc_out: device pointers of the TBCC decoder (None = not wanted)."""
+    _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("metric", C.c_void_p), ("tb_ok", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -127,6 +132,12 @@ PROTOTYPES = {
                                           C.POINTER(PilotOut), C.c_void_p]),
     "ofdm_rx_demod_frames_pilots": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                 C.c_int32, C.POINTER(PilotOut), C.POINTER(SoftOut), C.c_void_p]),
+    "ofdm_tbcc_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
+    "ofdm_tx_tbcc_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_int32, C.c_int64, C.c_void_p]),
+    "ofdm_rx_reserve_tbcc": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
+    "ofdm_tbcc_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(TbccOut),
+                                          C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

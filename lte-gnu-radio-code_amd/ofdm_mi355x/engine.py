@@ -79,6 +79,11 @@ def count_bit_errors(d_a, d_b, n_bytes: int, d_count, stream=None, device: int =
     check(_lib.load().ofdm_count_bit_errors(int(device), ptr(d_a), ptr(d_b), int(n_bytes), ptr(d_count), ptr(stream)))
 
 
+def tbcc_blocks(seg_bits: int, K: int) -> int:
+    """ofdm_tbcc_blocks: the TBCC code blocks of K information bits (3K coded bits each) a segment of seg_bits bits can carry."""
+    return int(check(_lib.load().ofdm_tbcc_blocks(int(seg_bits), int(K))))
+
+
 class RxEngine:
     """Receive chain handle (sync search, LS channel estimate, FFT + equalise, de-map)."""
 
@@ -225,6 +230,22 @@ class RxEngine:
         return int(check(self.lib.ofdm_rx_demod_frames_pilots(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
                                                               int(frame_len), ptr(d_eq), ptr(d_tsr), int(mode), C.byref(out),
                                                               C.byref(soft), ptr(stream))))
+
+    # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
+    def reserve_tbcc(self, n_blocks: int, K: int):
+        """Prepares decoding of up to n_blocks code blocks of K bits per call (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_tbcc(self._h, int(n_blocks), int(K)))
+
+    def tbcc_decode_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, d_bits=None, bits_mode=BITS_UNPACKED, d_metric=None,
+                           d_tb_ok=None, stream=None):
+        """ofdm_tbcc_decode_frames: block (s, b) = the 3K float32 LLRs at d_llr + s*seg_stride + b*3K (seg_stride in floats).
+        Outputs dense per block: bits [K] (one per byte, or packed MSB-first), metric float32, tb_ok int32."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
+        check(self.lib.ofdm_tbcc_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                               C.byref(out), ptr(stream)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -407,6 +428,13 @@ class TxEngine:
             frame_stride = n_sym * L
         check(self.lib.ofdm_tx_modulate_frames(self._h, ptr(d_bits), int(bits_mode), int(n_frames), int(n_sym),
                                                ptr(d_iq), int(frame_stride), ptr(stream)))
+
+    def tbcc_encode_frames(self, d_info, n_seg, blocks_per_seg, K, d_coded, seg_bits, info_mode=BITS_UNPACKED,
+                           coded_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_tbcc_encode_frames: d_info dense [n_seg][blocks_per_seg][K] bits -> d_coded [n_seg][seg_bits]: 3K coded bits per
+        block from bit 0 of the segment, then zeros; seg_bits = bits_per_frame(n_sym) feeds modulate_frames directly."""
+        check(self.lib.ofdm_tx_tbcc_encode_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
+                                                  ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
 
     # ---- decomposed stages (device buffers)
     def random_bits(self, seed, offset, d_bits, n_bits, stream=None):

@@ -38,7 +38,7 @@ def demangle(names):
 
 
 def short(name):
-    name = re.sub(r"^void ", "", name)
+    name = re.sub(r"^void ", "", name).replace("(anonymous namespace)::", "")
     name = re.sub(r"\(.*$", "", name)
     return name.replace("ofdm::", "").replace("(ofdm::DemodFlags)", "").replace("(DemodFlags)", "")
 
