@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import tbcc_cases as tc
 import tbcc_ref
 from conftest import ROOT
 
@@ -85,6 +86,81 @@ def test_awgn_blocks_decode_without_error_at_2_db_and_at_0_db(K, n_blocks):
         if esn0 == 2.0:
             assert raw >= 0.03
         assert wrong == 0
+
+
+# ------------------------------------------------------------------------------------------ inputs of the GPU edge tests
+# tests/test_gpu_tbcc_edges.py compares the kernels with tbcc_ref on the arrays of tests/tbcc_cases.py.  These tests show, on the
+# reference alone, that those arrays reach the paths they are there for, so that the comparison cannot pass without them.
+def test_edge_sweep_covers_every_tile_remainder_and_has_marginal_decisions():
+    assert len(tc.K_SWEEP) == 38 and all(tbcc_ref.valid_k(K) for K in tc.K_SWEEP)
+    assert {K % 64 for K in tc.K_SWEEP if K <= 256} == {K % 64 for K in tc.K_SWEEP if K >= 1992} == set(range(0, 64, 8))
+    assert set(range(24, 96, 8)) <= set(tc.K_SWEEP)                           # every K whose warm-up wraps more than once
+    wrong_total = 0
+    for K in tc.K_SWEEP:
+        llr, c, (bits, metric, ok) = tc.sweep_reference(K)
+        assert llr.shape == (8, 3 * K) and llr.dtype == np.float32
+        assert np.all(llr[4:7] == np.round(llr[4:7])) and np.abs(llr[4:6]).max() == 1 and np.abs(llr[6]).max() == 2
+        assert np.array_equal(bits[7], c[7]) and ok[7] == 1 and metric[7] == np.float32(3 * (K + 192))
+        wrong_total += int(np.any(bits[tc.SWEEP_AWGN] != c[tc.SWEEP_AWGN], axis=1).sum())
+    print("AWGN blocks of the sweep that decode wrongly: %d of %d" % (wrong_total, 4 * len(tc.K_SWEEP)))
+    assert wrong_total >= 1
+
+
+@pytest.mark.parametrize("lo,hi", tc.TIE_RANGES, ids=("pm1", "pm2"))
+@pytest.mark.parametrize("K", tc.TIE_KS)
+def test_edge_tie_inputs_hold_ties_failed_tail_biting_and_end_states_other_than_0(K, lo, hi):
+    llr = tc.tie_blocks(K, lo, hi)
+    assert llr.shape == (64, 3 * K) and llr.min() == lo and llr.max() == hi - 1
+    _, metric, ok = tbcc_ref.decode(llr)
+    st = tc.forward_stats(llr)
+    assert np.array_equal(st["metric"], metric)                               # the recount is the reference's recursion
+    n_fail = int((ok == 0).sum())
+    n_end = int((st["end_tied"] & (st["end_state"] != 0)).sum())
+    n_ties = int(st["ties"].sum())
+    print("K=%d [%d, %d): tb_ok = 0 in %d blocks, tied end states %d (%d not won by state 0), decision ties %d" % (
+        K, lo, hi, n_fail, int(st["end_tied"].sum()), n_end, n_ties))
+    assert n_fail >= 3
+    assert n_end >= 20
+    assert n_ties >= 10000
+
+
+def test_edge_scale_inputs_keep_bits_and_scale_the_metric_down_to_subnormals():
+    llr, _ = tc.scale_blocks()
+    assert llr.shape == (16, 360)
+    b0, m0, ok0 = tbcc_ref.decode(llr)
+    tiny = np.finfo(np.float32).tiny
+    for e in tc.SCALE_EXPONENTS:
+        x = tc.scaled(llr, e)
+        assert x.dtype == np.float32 and np.all(np.isfinite(x))
+        b, m, ok = tbcc_ref.decode(x)
+        assert np.array_equal(b, b0) and np.array_equal(ok, ok0), e
+        if e == -140:
+            # |llr| < 2^5 puts every product below 2^-126; the few with |llr| < 2^-10 round to 0 (P(|4y| < 2^-10) ~ 1e-4)
+            assert np.all(np.abs(x) < tiny) and np.count_nonzero(x) >= 0.99 * x.size, "every input is to be subnormal"
+            assert np.all(m != 0) and np.all(np.abs(m) < tiny)
+        else:
+            assert np.array_equal(m, np.ldexp(m0, e).astype(np.float32)) and np.all(np.isfinite(m)), e
+    x = tc.scaled(llr, -126)                                                  # normal and subnormal inputs side by side
+    assert 0 < int((np.abs(x) < tiny).sum()) < x.size
+
+
+def test_edge_output_grid_and_encoder_inputs_have_the_stated_shapes():
+    for K in tc.OUTPUT_KS:
+        seg = tc.output_segments(K)
+        assert seg.shape == (2, 5 * 3 * K + 7) and np.isnan(seg[:, 5 * 3 * K:]).all() and np.isfinite(seg[:, :5 * 3 * K]).all()
+        assert seg.shape[1] % 2 == 1                                          # a stride that moves every second segment off 8 bytes
+    src = tc.grid_source()
+    _, _, ok = tbcc_ref.decode(src)
+    assert 0 < int(ok.sum()) < 16, "the tiled blocks are to hold both values of tb_ok"
+    seg = tc.grid_segments(src)
+    assert seg.shape == (7000, 725) and 7000 * 10 > 65535
+    flat = seg[:, :720].reshape(70000, 72)
+    assert np.array_equal(flat[16 * 4000 + 5], src[5]) and np.array_equal(flat[69999], src[69999 % 16])
+    for K in (24, 2048):
+        imp = tc.impulse_info(K)
+        assert imp.shape == (2, 3, K) and np.all(imp.sum(axis=2) == 1)
+        assert [int(np.argmax(r)) for r in imp.reshape(6, K)] == [0, 1, 5, 6, K - 6, K - 1]
+        assert np.all(tbcc_ref.encode(imp).sum(axis=2) == 15)
 
 
 # ------------------------------------------------------------------------------------------ host side of the entry points
