@@ -589,7 +589,10 @@ __global__ void __launch_bounds__(256) tx_mux_kernel(TxDev tx, MuxArgs a) {
 // Two consecutive output samples per thread: one Philox4x32-10 block (four 32-bit words) feeds both Box-Muller pairs, and the
 // pair leaves in one 16-byte store where the row is aligned.  Noise is N(0, noise_std^2) per component from the hardware
 // transcendentals (v_log_f32, v_sqrt_f32, v_sin_f32 / v_cos_f32 take their argument in revolutions): a statistical model of
-// MultiAntennaSystem.py:258, not a bit-pinned one.
+// MultiAntennaSystem.py:258, not a bit-pinned one with respect to the reference's NumPy generator.  The stream itself IS pinned:
+// counter layout, word-to-sample assignment and the u formula are the contract written at ofdm_channel_apply in
+// include/ofdm_mi355x.h (a sample's noise depends on seed, frame and sample index only); tests/test_gpu_channel_edges.py holds
+// every sample against it.  The loop's stride is the whole grid: launch_channel caps the grid, longer frames take further trips.
 __global__ void __launch_bounds__(256) channel_kernel(ChanArgs a) {
     const int frame = blockIdx.y;
     const cf* in = a.in + int64_t(frame) * a.in_stride;
