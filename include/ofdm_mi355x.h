@@ -308,9 +308,9 @@ int ofdm_channel_apply(ofdm_tx* h, const float* d_in, int64_t n_frames, int64_t 
 /* ------------------------------------------------------------------------------------------ channel code (LTE TBCC)
  * The tail-biting convolutional code of 3GPP TS 36.212 5.1.3.1 on the frame-batched path: an encoder in front of
  * ofdm_tx_modulate_frames and a decoder behind the LLRs of ofdm_demap_frames / ofdm_rx_demod_frames_soft /
- * ofdm_rx_demod_frames_pilots.  An extension: the reference has no channel code, so this text is the contract.  The sub-block
- * interleaver and the circular-buffer rate matching of 5.1.4.2 are NOT part of it: the coded order is the plain interleaving
- * below and the rate is always 1/3.
+ * ofdm_rx_demod_frames_pilots.  An extension: the reference has no channel code, so this text is the contract.  The calls of
+ * this block use the plain interleaving below at rate 1/3; the sub-block interleaver and the circular-buffer rate matching of
+ * 5.1.4.2 are the ofdm_*_rm_* calls of the next block, which leave these calls as they are.
  * Code block: K information bits c[0..K), K a multiple of 8 with 24 <= K <= 2048; indices are taken mod K (tail-biting: the
  * register starts in the state of the last six bits).
  * Encoder:  d0[k] = c[k]^c[k-2]^c[k-3]^c[k-5]^c[k-6]   (generator 133 octal)
@@ -350,8 +350,8 @@ typedef struct ofdm_tbcc_out {   /* DEVICE pointers; NULL = not wanted */
     int32_t* tb_ok;      /* [n_seg][blocks_per_seg]                                                                            */
 } ofdm_tbcc_out;
 /* Prepares the handle's device for decoding up to n_blocks blocks of K bits per call: the decoder keeps its survivors in LDS and
- * needs no device workspace, so this checks the geometry and loads the kernel.  Call it before capturing ofdm_tbcc_decode_frames
- * into a hipGraph. */
+ * needs no device workspace, so this checks the geometry and loads the kernels.  Call it before capturing ofdm_tbcc_decode_frames
+ * or ofdm_tbcc_decode_rm_frames into a hipGraph. */
 int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K);
 /* Block (s, b) reads the 3K float32 LLRs at d_llr + s*seg_stride + b*3K (seg_stride in floats, >= blocks_per_seg*3K), so the
  * call works on any LLR buffer.  Asynchronous on `stream` (NULL = the handle's stream): one launch, no host synchronisation and
@@ -360,6 +360,46 @@ int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K);
  * before anything is enqueued and without touching the device. */
 int ofdm_tbcc_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
                             const ofdm_tbcc_out* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------ rate matching (LTE TBCC)
+ * The sub-block interleaver and the circular buffer of TS 36.212 5.1.4.2 around the code above: E rate-matched bits per block
+ * in place of the 3K of e[3k+j] (puncturing for E < 3K, repetition for E > 3K), on the transmit side as an encoder of its own and
+ * on the receive side as a de-matching stage and as a decoder that de-matches while it loads.  An extension like the code
+ * itself: this text is the contract.
+ * K as above (D = K); 1 <= E <= 48K (at most 16 copies of a coded bit; PBCH's 1920 / 120 is exactly 16).  R = ceil(K / 32),
+ * ND = 32R - K.
+ * Sub-block interleaver: each stream dj, prefixed with ND NULLs, is written row by row into an R x 32 matrix; column c of the
+ *   permuted matrix is column P[c] of it, P = <1,17,9,25,5,21,13,29,3,19,11,27,7,23,15,31,0,16,8,24,4,20,12,28,2,18,10,26,6,22,14,30>
+ *   (P[c] is the 5-bit reversal of (c + 16) mod 32); the permuted matrix read column by column is vj, 32R entries.
+ * Circular buffer: w = v0 | v1 | v2; e_k, k = 0 .. E-1, walks w cyclically from index 0 and skips the NULLs (k0 = 0: the
+ *   convolutionally coded channels have no other start).
+ * Closed form: nullmask has bit c set iff P[c] < ND.  Coded bit dj[i] has y = ND + i, row = y >> 5, c = P^-1[y & 31] and the
+ *   rank  q = j K + c R + row - popcount(nullmask & ((2 << c) - 1)),  0 <= q < 3K;  e_k = the coded bit of rank k mod 3K.
+ *   The other way: cum(c) = c R - popcount(nullmask & ((1 << c) - 1)); inside stream j, c is the largest column with
+ *   cum(c) <= rank, row = rank - cum(c) + [P[c] < ND], i = 32 row + P[c] - ND.  E = 3K is a permutation of the 3K coded bits.
+ * Segments: as above with E in place of 3K -- block b has its coded bits at segment bit b*E and its LLRs at
+ *   d_llr + s*seg_stride + b*E; blocks_per_seg*E <= seg_bits (encoder), seg_stride >= blocks_per_seg*E (receive side); filler
+ *   zeros follow the last block.  E need not be a multiple of 8: packed blocks may start inside a byte.
+ * De-matching, IEEE float32 in this order: v(x) = x if x is finite, else 0.  For rank q: L = +0 if q >= E (punctured), else
+ *   L = v(l[q]) and then L = L + v(l[q + m 3K]) for m = 1, 2, .. while the index is < E, in increasing m.  The decoder uses
+ *   v(L) -- a sum that overflowed counts as 0, as any input that is not finite does -- and is the decoder above from there on.
+ * Deterministic: a block's outputs depend on its own E LLRs only (no atomics). */
+/* floor(seg_bits / E): the blocks a segment can carry.  Host arithmetic; OFDM_ERR_INVALID for a bad K, E or seg_bits < 0. */
+int64_t ofdm_tbcc_rm_blocks(int64_t seg_bits, int32_t K, int32_t E);
+/* ofdm_tx_tbcc_encode_frames with E rate-matched bits per block; the same layouts, rules and errors (seg_bits >= blocks_per_seg*E). */
+int ofdm_tx_tbcc_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                  int32_t K, int32_t E, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream);
+/* De-matching alone: d_out[s*out_stride + b*3K + 3i + j] = L of dj[i] (out_stride in floats, >= blocks_per_seg*3K), the layout
+ * ofdm_tbcc_decode_frames reads.  L is stored as summed (an overflowed sum as +-inf, a single -0 as -0).  Asynchronous, one
+ * launch, no allocation; n_seg == 0 or blocks_per_seg == 0 is a no-op; argument errors as below. */
+int ofdm_tbcc_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                                  int32_t K, int32_t E, float* d_out, int64_t out_stride, void* stream);
+/* ofdm_tbcc_decode_frames on rate-matched LLRs, de-matched while they are loaded: one launch and no 3K-float intermediate; the
+ * outputs are those of ofdm_tbcc_rate_dematch_frames followed by ofdm_tbcc_decode_frames, bit for bit.  The same rules as
+ * ofdm_tbcc_decode_frames (ofdm_rx_reserve_tbcc prepares this call too); OFDM_ERR_INVALID before anything is enqueued for a NULL
+ * handle, a bad K, E outside 1 .. 48K, seg_stride < blocks_per_seg*E, a negative count or a batch beyond the index range. */
+int ofdm_tbcc_decode_rm_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                               int32_t K, int32_t E, const ofdm_tbcc_out* out, void* stream);
 
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the

@@ -2231,8 +2231,8 @@ int ofdm_tx_tbcc_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_m
 }
 
 // The decoder keeps its survivors in LDS and has no device workspace, so there is nothing to allocate: the call checks the
-// geometry a later decode will use and loads the kernel's code object, which is the one piece of set-up a first launch would
-// otherwise do inside a capture.
+// geometry a later decode will use and loads the code objects of both decoders (plain and rate-matched), which is the one piece
+// of set-up a first launch would otherwise do inside a capture.
 int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K) {
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tbcc: null handle");
     const char* bad = tbcc_bad_geometry(1, n_blocks, K);
@@ -2267,6 +2267,111 @@ int ofdm_tbcc_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64
     a.tb_ok = out->tb_ok;
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(launch_tbcc_decode(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return OFDM_OK;
+}
+
+// ---- rate matching of the same code (TS 36.212 5.1.4.2; definition: include/ofdm_mi355x.h)
+namespace {
+// argument check shared by the rate-matched calls (no device access); "" = fine
+const char* tbcc_rm_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K, int64_t E) {
+    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
+    if (*bad) return bad;
+    if (!tbcc_valid_e(K, E)) return "E must lie in 1 .. 48K";
+    return "";
+}
+bool tbcc_items_ok(int64_t n_seg, int64_t per_seg) { return per_seg <= TBCC_MAX_ITEMS && (n_seg <= 0 || per_seg <= TBCC_MAX_ITEMS / n_seg); }
+}  // namespace
+
+int64_t ofdm_tbcc_rm_blocks(int64_t seg_bits, int32_t K, int32_t E) {
+    const char* bad = tbcc_rm_bad_geometry(0, 0, K, E);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rm_blocks: %s", bad);
+    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rm_blocks: negative seg_bits");
+    return seg_bits / E;
+}
+
+int ofdm_tx_tbcc_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                  int32_t K, int32_t E, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: null handle");
+    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: %s", bad);
+    if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode))
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+    if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * E)
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: seg_bits < blocks_per_seg * E");
+    if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7))
+        return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: packed coded bits need seg_bits %% 8 == 0");
+    if (!tbcc_items_ok(n_seg, seg_bits)) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: batch beyond the kernel's index range");
+    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
+    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: null buffer");
+    TbccEncRmArgs a{};
+    a.info = d_info;
+    a.info_mode = info_mode;
+    a.n_seg = n_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.coded = d_coded;
+    a.coded_mode = coded_mode;
+    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    a.g = tbcc_rm_geom(K, E);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_tbcc_encode_rm(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return OFDM_OK;
+}
+
+int ofdm_tbcc_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                                  int32_t K, int32_t E, float* d_out, int64_t out_stride, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: null handle");
+    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: %s", bad);
+    if (seg_stride < int64_t(blocks_per_seg) * E)
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: seg_stride < blocks_per_seg * E");
+    if (out_stride < int64_t(blocks_per_seg) * 3 * K)
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: out_stride < blocks_per_seg * 3K");
+    // one thread per output LLR in workgroups of 256: the grid's x range bounds n_seg * blocks_per_seg * 3K
+    if (!tbcc_items_ok(n_seg, seg_stride) || !tbcc_items_ok(n_seg, out_stride) ||
+        n_seg * int64_t(blocks_per_seg) > TBCC_MAX_BLOCKS * int64_t(256) / (3 * K))
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: batch beyond the kernel's index range");
+    if (n_seg == 0 || blocks_per_seg == 0) return OFDM_OK;
+    if (!d_llr || !d_out) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: null buffer");
+    TbccDematchArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_seg * blocks_per_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.out = d_out;
+    a.out_stride = out_stride;
+    a.g = tbcc_rm_geom(K, E);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_tbcc_dematch(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return OFDM_OK;
+}
+
+int ofdm_tbcc_decode_rm_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                               int32_t K, int32_t E, const ofdm_tbcc_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: null handle");
+    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: %s", bad);
+    if (seg_stride < int64_t(blocks_per_seg) * E)
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: seg_stride < blocks_per_seg * E");
+    if (!tbcc_items_ok(n_seg, seg_stride)) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: batch beyond the kernel's index range");
+    if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode))
+        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED");
+    if (n_seg == 0 || blocks_per_seg == 0 || !out || (!out->bits && !out->metric && !out->tb_ok)) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: null d_llr");
+    TbccDecRmArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_seg * blocks_per_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.bits = out->bits;
+    a.bits_mode = out->bits_mode;
+    a.metric = out->metric;
+    a.tb_ok = out->tb_ok;
+    a.g = tbcc_rm_geom(K, E);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_tbcc_decode_rm(a, stream ? static_cast<hipStream_t>(stream) : h->stream));
     return OFDM_OK;
 }
 

@@ -236,9 +236,32 @@ struct TbccDecArgs {
     float* metric;           // [n_blocks], or null
     int32_t* tb_ok;          // [n_blocks], or null
 };
+// Rate matching (TS 36.212 5.1.4.2): what the sub-block interleaver's closed form needs, all of it from K
+constexpr int TBCC_RM_MAX_COPIES = 16;   // E <= 3K * 16
+inline bool tbcc_valid_e(int64_t K, int64_t E) { return E >= 1 && E <= 3 * TBCC_RM_MAX_COPIES * K; }
+struct TbccRmGeom {
+    int E;                   // rate-matched bits per block
+    int R, ND;               // rows of the 32-column matrix = ceil(K / 32), NULLs in front of a stream = 32R - K
+    uint32_t nullmask;       // bit c set iff permuted column c starts with a NULL: P[c] < ND
+};
+TbccRmGeom tbcc_rm_geom(int K, int E);
+struct TbccEncRmArgs : TbccEncArgs { TbccRmGeom g; };       // coded: blocks_per_seg*E bits from bit 0, then zeros
+struct TbccDecRmArgs : TbccDecArgs { TbccRmGeom g; };       // llr: block (seg, b) = E floats at llr + seg*seg_stride + b*E
+struct TbccDematchArgs {
+    const float* llr;        // block (seg, b) = E floats at llr + seg*seg_stride + b*E
+    int64_t seg_stride;      // floats
+    int64_t n_blocks;        // n_seg * blocks_per_seg
+    int blocks_per_seg, K;
+    float* out;              // block (seg, b) = 3K floats at out + seg*out_stride + b*3K, [3i + j]: what TbccDecArgs::llr takes
+    int64_t out_stride;      // floats
+    TbccRmGeom g;
+};
 hipError_t launch_tbcc_encode(const TbccEncArgs& a, hipStream_t s);
 hipError_t launch_tbcc_decode(const TbccDecArgs& a, hipStream_t s);
-// loads the decoder's code object (so that a first launch inside a stream capture has nothing left to set up)
+hipError_t launch_tbcc_encode_rm(const TbccEncRmArgs& a, hipStream_t s);
+hipError_t launch_tbcc_dematch(const TbccDematchArgs& a, hipStream_t s);
+hipError_t launch_tbcc_decode_rm(const TbccDecRmArgs& a, hipStream_t s);
+// loads the decoders' code objects (so that a first launch inside a stream capture has nothing left to set up)
 hipError_t tbcc_decode_prepare();
 size_t tbcc_lds_bytes(int K);            // survivor memory of one block: 8 B per trellis step, rounded up to 32 steps
 

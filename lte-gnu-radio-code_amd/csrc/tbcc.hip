@@ -1,10 +1,12 @@
 // tbcc.hip -- LTE tail-biting convolutional code (TS 36.212 5.1.3.1: constraint length 7, rate 1/3, generators 133 / 171 / 165)
 // on the frame-batched path: encoder in front of ofdm_tx_modulate_frames, wrap-around Viterbi decoder behind the per-frame LLRs.
-// The definition both kernels implement is the contract in include/ofdm_mi355x.h; the reference has no
-// channel code, so there is nothing in it to cite.
+// Around it the sub-block interleaver and circular-buffer rate matching of 5.1.4.2: an encoder of its own, a de-matching kernel
+// and the decoder's RM instantiation, which de-matches in its tile load.  The definition the kernels implement is the contract
+// in include/ofdm_mi355x.h; the reference has no channel code, so there is nothing in it to cite.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 #include "ofdm_launch.hpp"
 
 namespace ofdm {
@@ -18,13 +20,8 @@ __device__ __forceinline__ unsigned tbcc_info_bit(const uint8_t* blk, int packed
     return packed ? (unsigned(blk[i >> 3]) >> (7 - (i & 7))) & 1u : unsigned(blk[i]) & 1u;
 }
 
-// coded bit q of a segment (0 past the last block: filler)
-__device__ __forceinline__ unsigned tbcc_coded_bit(const uint8_t* seg_info, int info_packed, int K, int64_t coded_per_seg, int64_t q) {
-    if (q >= coded_per_seg) return 0u;
-    const int b = int(q / (3 * K));
-    const int r = int(q - int64_t(b) * 3 * K);
-    const int k = r / 3, j = r - 3 * k;
-    const uint8_t* blk = seg_info + int64_t(b) * (info_packed ? K >> 3 : K);
+// dj[k] of the block at blk: the parity of generator j over the 7-bit window that ends at k
+__device__ __forceinline__ unsigned tbcc_stream_bit(const uint8_t* blk, int info_packed, int K, int k, int j) {
     unsigned reg = 0u;                                   // bit 6-i = c[(k - i) mod K]
 #pragma unroll
     for (int i = 0; i < 7; ++i) {
@@ -34,6 +31,15 @@ __device__ __forceinline__ unsigned tbcc_coded_bit(const uint8_t* seg_info, int 
     }
     const unsigned g = j == 0 ? TBCC_G0 : j == 1 ? TBCC_G1 : TBCC_G2;
     return unsigned(__popc(reg & g)) & 1u;
+}
+
+// coded bit q of a segment (0 past the last block: filler)
+__device__ __forceinline__ unsigned tbcc_coded_bit(const uint8_t* seg_info, int info_packed, int K, int64_t coded_per_seg, int64_t q) {
+    if (q >= coded_per_seg) return 0u;
+    const int b = int(q / (3 * K));
+    const int r = int(q - int64_t(b) * 3 * K);
+    const int k = r / 3, j = r - 3 * k;
+    return tbcc_stream_bit(seg_info + int64_t(b) * (info_packed ? K >> 3 : K), info_packed, K, k, j);
 }
 
 // One thread per 4 output bytes of a segment (4 coded bits one per byte, or 32 packed MSB-first), stored as one word where the
@@ -68,6 +74,100 @@ __global__ void __launch_bounds__(256) tbcc_encode_kernel(TbccEncArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------ rate matching
+// The sub-block interleaver in closed form (include/ofdm_mi355x.h): P[c] is the 5-bit reversal of c ^ 16, so neither P nor its
+// inverse is a table, and the NULLs in front of a column are a popcount of the 32-bit mask of the columns that start with one.
+__device__ __forceinline__ int tbcc_rm_perm(int c) { return int(__brev(unsigned(c) ^ 16u) >> 27); }        // P[c]
+__device__ __forceinline__ int tbcc_rm_perm_inv(int x) { return int(__brev(unsigned(x)) >> 27) ^ 16; }     // P^-1[x]
+// rank of d0[i] among the 3K coded bits of the circular buffer; dj[i] sits j*K behind it
+__device__ __forceinline__ int tbcc_rm_rank0(const TbccRmGeom& g, int i) {
+    const int y = g.ND + i, c = tbcc_rm_perm_inv(y & 31);
+    return c * g.R + (y >> 5) - __popc(g.nullmask & ((2u << c) - 1u));
+}
+// coded bits in front of column c of one stream
+__device__ __forceinline__ int tbcc_rm_cum(const TbccRmGeom& g, int c) { return c * g.R - __popc(g.nullmask & ((1u << c) - 1u)); }
+// rank r inside a stream (0 <= r < K) -> i: the largest column with cum(c) <= r (cum does not decrease: five halvings), then the row
+__device__ __forceinline__ int tbcc_rm_index(const TbccRmGeom& g, int r) {
+    int c = 0;
+#pragma unroll
+    for (int bit = 16; bit; bit >>= 1)
+        if (tbcc_rm_cum(g, c | bit) <= r) c |= bit;
+    const int p = tbcc_rm_perm(c);
+    return 32 * (r - tbcc_rm_cum(g, c) + (p < g.ND ? 1 : 0)) + p - g.ND;
+}
+
+// The plain encoder's shape: one thread per 4 output bytes, a whole-word store where the address allows it, the filler written by
+// the same threads.  A thread divides once for its first bit and steps (block, bit of the block, rank) from there; every
+// output bit is a gather from the information bits: rank -> (j, i) -> the window parity, no d streams in between.
+__global__ void __launch_bounds__(256) tbcc_encode_rm_kernel(TbccEncRmArgs a) {
+    const int64_t words_per_seg = (a.seg_bytes + 3) >> 2;
+    const int64_t total = a.n_seg * words_per_seg;
+    const int64_t g = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= total) return;
+    const int64_t seg = g / words_per_seg, w = g - seg * words_per_seg;
+    const int info_packed = a.info_mode == 1, coded_packed = a.coded_mode == 1;
+    const int K = a.K, E = a.g.E, blk_bytes = info_packed ? K >> 3 : K;
+    const uint8_t* seg_info = a.info + seg * int64_t(a.blocks_per_seg) * blk_bytes;
+    const int64_t coded_per_seg = int64_t(a.blocks_per_seg) * E;
+    const int64_t byte0 = w << 2;
+    const int nbytes = int(std::min<int64_t>(4, a.seg_bytes - byte0));
+    const int nbits = coded_packed ? nbytes << 3 : nbytes;
+    const int64_t q0 = coded_packed ? byte0 << 3 : byte0;
+    int64_t b = q0 / E;
+    int k = int(q0 - b * E);
+    int rank = k % (3 * K);
+    uint32_t word = 0u;
+    for (int x = 0; x < nbits; ++x) {
+        if (q0 + x < coded_per_seg) {
+            const int j = rank >= 2 * K ? 2 : rank >= K ? 1 : 0;
+            const unsigned v = tbcc_stream_bit(seg_info + b * blk_bytes, info_packed, K, tbcc_rm_index(a.g, rank - j * K), j);
+            word |= v << (coded_packed ? (x & ~7) + 7 - (x & 7) : 8 * x);
+        }
+        if (++rank == 3 * K) rank = 0;
+        if (++k == E) {
+            k = 0;
+            rank = 0;
+            ++b;
+        }
+    }
+    uint8_t* dst = a.coded + seg * a.seg_bytes + byte0;
+    if (nbytes == 4 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0) {
+        *reinterpret_cast<uint32_t*>(dst) = word;
+    } else {
+        for (int y = 0; y < nbytes; ++y) dst[y] = uint8_t(word >> (8 * y));
+    }
+}
+
+__device__ __forceinline__ float tbcc_finite_or_zero(float v) {
+    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
+}
+
+// De-matching of one coded bit: l = the block's E LLRs, q = the bit's rank, n3 = 3K.  The copies are added in increasing index,
+// one float32 addition each; a punctured bit is +0.  No product: nothing here for the compiler to contract.
+__device__ __forceinline__ float tbcc_rm_combine(const float* l, int E, int n3, int q) {
+    float L = 0.f;
+    if (q < E) {
+        L = tbcc_finite_or_zero(l[q]);
+        for (int idx = q + n3; idx < E; idx += n3) L = L + tbcc_finite_or_zero(l[idx]);
+    }
+    return L;
+}
+
+// Stand-alone de-matching: one thread per output LLR (segment, block, 3i + j), the grid is exactly the work.  The stores are
+// coalesced; the <= 16 reads per thread are scattered over the block's own E floats.
+__global__ void __launch_bounds__(256) tbcc_dematch_kernel(TbccDematchArgs a) {
+    const int n3 = 3 * a.K;
+    const int64_t g = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (g >= a.n_blocks * n3) return;
+    const int64_t blk = g / n3;
+    const int x = int(g - blk * n3);
+    const int64_t seg = blk / a.blocks_per_seg;
+    const int b = int(blk - seg * a.blocks_per_seg);
+    const int i = x / 3, j = x - 3 * i;
+    const float* l = a.llr + seg * a.seg_stride + int64_t(b) * a.g.E;
+    a.out[seg * a.out_stride + int64_t(b) * n3 + x] = tbcc_rm_combine(l, a.g.E, n3, tbcc_rm_rank0(a.g, i) + j * a.K);
+}
+
 // ------------------------------------------------------------------------------------------ decoder
 // One wave per code block, lane = trellis state s'.  The path metric lives in one VGPR; the metrics of the two predecessors
 // p0 = (s' << 1) & 63 and p0 | 1 come over ds_bpermute with lane-constant addresses.  The LLRs of 64 consecutive steps are loaded
@@ -86,18 +186,25 @@ __device__ __forceinline__ float tbcc_readlane(float v, int lane) {
 __device__ __forceinline__ float tbcc_bperm(int byte_addr, float v) {
     return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
 }
-__device__ __forceinline__ float tbcc_finite_or_zero(float v) {
-    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
-}
 
-__global__ void __launch_bounds__(64) tbcc_viterbi_kernel(TbccDecArgs a) {
+// RM = false is the plain decoder.  RM = true de-matches in the tile load: the lane that owns step t takes its three LLRs
+// straight from the block's E rate-matched floats (tbcc_rm_combine, and a sum that is not finite counts as 0 like any other
+// input), so a rate-matched block is decoded in one launch with no 3K-float intermediate.  Everything behind the tile load is
+// shared.
+template <bool RM>
+__global__ void __launch_bounds__(64) tbcc_viterbi_kernel(std::conditional_t<RM, TbccDecRmArgs, TbccDecArgs> a) {
     extern __shared__ uint32_t sm[];                         // [ceil(T / 32)][64]
     const int lane = int(threadIdx.x);
     const int K = a.K, W = TBCC_W, T = K + 2 * TBCC_W;
     const int64_t blk = int64_t(blockIdx.x);
     const int64_t seg = blk / a.blocks_per_seg;
     const int b = int(blk - seg * a.blocks_per_seg);
-    const float* llr = a.llr + seg * a.seg_stride + int64_t(b) * 3 * K;
+    const float* llr;
+    if constexpr (RM) {
+        llr = a.llr + seg * a.seg_stride + int64_t(b) * a.g.E;
+    } else {
+        llr = a.llr + seg * a.seg_stride + int64_t(b) * 3 * K;
+    }
 
     const int p0 = (lane << 1) & 63;
     const unsigned tr = (unsigned(lane >> 5) << 6) | unsigned(p0);      // transition p0 -> s' with the input bit on top
@@ -111,9 +218,16 @@ __global__ void __launch_bounds__(64) tbcc_viterbi_kernel(TbccDecArgs a) {
         float l0 = 0.f, l1 = 0.f, l2 = 0.f;
         if (base + lane < T) {
             const int i = (base + lane + 4 * K - W) % K;     // (t - W) mod K; 4K >= W for every K >= 24
-            l0 = tbcc_finite_or_zero(llr[3 * i]);
-            l1 = tbcc_finite_or_zero(llr[3 * i + 1]);
-            l2 = tbcc_finite_or_zero(llr[3 * i + 2]);
+            if constexpr (RM) {
+                const int q = tbcc_rm_rank0(a.g, i);
+                l0 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q));
+                l1 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + K));
+                l2 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + 2 * K));
+            } else {
+                l0 = tbcc_finite_or_zero(llr[3 * i]);
+                l1 = tbcc_finite_or_zero(llr[3 * i + 1]);
+                l2 = tbcc_finite_or_zero(llr[3 * i + 2]);
+            }
         }
         for (int h = 0; h < 2; ++h) {
             const int n = std::min(32, T - base - 32 * h);   // a multiple of 8: K % 8 == 0
@@ -209,13 +323,47 @@ hipError_t launch_tbcc_encode(const TbccEncArgs& a, hipStream_t s) {
 
 hipError_t launch_tbcc_decode(const TbccDecArgs& a, hipStream_t s) {
     if (a.n_blocks <= 0) return hipSuccess;
-    hipLaunchKernelGGL(tbcc_viterbi_kernel, dim3(unsigned(a.n_blocks)), dim3(64), tbcc_lds_bytes(a.K), s, a);
+    hipLaunchKernelGGL(tbcc_viterbi_kernel<false>, dim3(unsigned(a.n_blocks)), dim3(64), tbcc_lds_bytes(a.K), s, a);
+    return hipGetLastError();
+}
+
+TbccRmGeom tbcc_rm_geom(int K, int E) {
+    TbccRmGeom g{};
+    g.E = E;
+    g.R = (K + 31) / 32;
+    g.ND = 32 * g.R - K;
+    for (unsigned c = 0; c < 32; ++c) {
+        unsigned x = c ^ 16u, p = 0u;                        // P[c]: the 5-bit reversal of c ^ 16
+        for (int bit = 0; bit < 5; ++bit) p |= ((x >> bit) & 1u) << (4 - bit);
+        if (int(p) < g.ND) g.nullmask |= 1u << c;
+    }
+    return g;
+}
+
+hipError_t launch_tbcc_encode_rm(const TbccEncRmArgs& a, hipStream_t s) {
+    const int64_t total = a.n_seg * ((a.seg_bytes + 3) >> 2);
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tbcc_encode_rm_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tbcc_dematch(const TbccDematchArgs& a, hipStream_t s) {
+    const int64_t total = a.n_blocks * 3 * a.K;
+    if (total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tbcc_dematch_kernel, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tbcc_decode_rm(const TbccDecRmArgs& a, hipStream_t s) {
+    if (a.n_blocks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tbcc_viterbi_kernel<true>, dim3(unsigned(a.n_blocks)), dim3(64), tbcc_lds_bytes(a.K), s, a);
     return hipGetLastError();
 }
 
 hipError_t tbcc_decode_prepare() {
     hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(tbcc_viterbi_kernel));
+    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(tbcc_viterbi_kernel<false>));
+    return e != hipSuccess ? e : hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(tbcc_viterbi_kernel<true>));
 }
 
 }  // namespace ofdm

@@ -138,6 +138,13 @@ PROTOTYPES = {
     "ofdm_rx_reserve_tbcc": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "ofdm_tbcc_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(TbccOut),
                                           C.c_void_p]),
+    "ofdm_tbcc_rm_blocks": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "ofdm_tx_tbcc_encode_rm_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ofdm_tbcc_rate_dematch_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                C.c_void_p, C.c_int64, C.c_void_p]),
+    "ofdm_tbcc_decode_rm_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             C.POINTER(TbccOut), C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

@@ -84,6 +84,11 @@ def tbcc_blocks(seg_bits: int, K: int) -> int:
     return int(check(_lib.load().ofdm_tbcc_blocks(int(seg_bits), int(K))))
 
 
+def tbcc_rm_blocks(seg_bits: int, K: int, E: int) -> int:
+    """ofdm_tbcc_rm_blocks: the rate-matched TBCC code blocks (K information bits in E coded bits) a segment of seg_bits carries."""
+    return int(check(_lib.load().ofdm_tbcc_rm_blocks(int(seg_bits), int(K), int(E))))
+
+
 class RxEngine:
     """Receive chain handle (sync search, LS channel estimate, FFT + equalise, de-map)."""
 
@@ -246,6 +251,24 @@ class RxEngine:
         out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
         check(self.lib.ofdm_tbcc_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                C.byref(out), ptr(stream)))
+
+    # ---- the same code behind the rate matching of TS 36.212 5.1.4.2: E LLRs per block in place of 3K ----
+    def tbcc_rate_dematch_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, E, d_out, out_stride, stream=None):
+        """ofdm_tbcc_rate_dematch_frames: block (s, b) = the E float32 LLRs at d_llr + s*seg_stride + b*E -> its 3K de-matched
+        LLRs at d_out + s*out_stride + b*3K, the layout tbcc_decode_frames reads (strides in floats)."""
+        check(self.lib.ofdm_tbcc_rate_dematch_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                                     int(E), ptr(d_out), int(out_stride), ptr(stream)))
+
+    def tbcc_decode_rm_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, E, d_bits=None, bits_mode=BITS_UNPACKED,
+                              d_metric=None, d_tb_ok=None, stream=None):
+        """ofdm_tbcc_decode_rm_frames: tbcc_decode_frames on rate-matched LLRs (block (s, b) = E floats at d_llr + s*seg_stride +
+        b*E), de-matched inside the decoder's launch.  reserve_tbcc prepares this call too."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
+        check(self.lib.ofdm_tbcc_decode_rm_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                                  int(E), C.byref(out), ptr(stream)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -435,6 +458,13 @@ class TxEngine:
         block from bit 0 of the segment, then zeros; seg_bits = bits_per_frame(n_sym) feeds modulate_frames directly."""
         check(self.lib.ofdm_tx_tbcc_encode_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
                                                   ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
+
+    def tbcc_encode_rm_frames(self, d_info, n_seg, blocks_per_seg, K, E, d_coded, seg_bits, info_mode=BITS_UNPACKED,
+                              coded_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_tbcc_encode_rm_frames: tbcc_encode_frames with the sub-block interleaver and circular-buffer rate matching of
+        TS 36.212 5.1.4.2: E coded bits per block from bit 0 of the segment, then zeros."""
+        check(self.lib.ofdm_tx_tbcc_encode_rm_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
+                                                     int(E), ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
 
     # ---- decomposed stages (device buffers)
     def random_bits(self, seed, offset, d_bits, n_bits, stream=None):

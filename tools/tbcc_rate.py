@@ -40,7 +40,7 @@ def inner_loop_mix():
     """-> dict(v=, ds=, s=, w=, total=) per trellis step from the code object, or None without a compiler"""
     try:
         out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "dev", "isa_blocks.py"), "tbcc.hip",
-                              r"_ZN4ofdm\w*tbcc_viterbi_kernel"], check=True, capture_output=True, text=True).stdout
+                              r"_ZN4ofdm\w*tbcc_viterbi_kernelILb0"], check=True, capture_output=True, text=True).stdout
     except (OSError, subprocess.CalledProcessError):
         return None
     best = None
