@@ -1,0 +1,323 @@
+// capi_internal.hpp -- what the host-only units of the C ABI (capi_*.hip) share: the error plumbing, the four handle structs
+// and the small helpers of their create / destroy / reserve / per-call paths.  Nothing in here is exported.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <complex>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/ofdm_mi355x.h"
+#ifdef OFDM_EXPERIMENTS
+#include "../../tools/experiments/ofdm_experiments.h"
+#endif
+#include "ofdm_launch.hpp"
+
+using namespace ofdm;
+
+// ---- defined once, in capi_common.hip
+#pragma GCC visibility push(hidden)
+int fail(int code, const char* fmt, ...);                              // sets ofdm_last_error(), returns code
+std::vector<cf> make_twiddles(int n);
+std::vector<cf> make_zc(int mm, int root, int parity_of);
+std::vector<cf> make_scan_table(int N, int Ks, const std::vector<cf>& zc);
+int fill_rxdev(const ofdm_rx_cfg& cfg, RxDev& d);                      // derived constants; returns the Zadoff-Chu root
+int upload_rx_tables(RxDev& d, cf** d_tw, cf** d_zc, const std::vector<cf>& zc);
+#pragma GCC visibility pop
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(OFDM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
+    } while (0)
+
+struct ofdm_rx {
+    ofdm_rx_cfg cfg{};
+    hipStream_t stream = nullptr;
+    hipStream_t stream2 = nullptr;       // stream block: the first stage of the sync search runs here, under the rest of the upload
+    hipEvent_t ev_up = nullptr, ev_s1 = nullptr;
+    RxDev dev{};
+    cf* d_tw = nullptr;
+    cf* d_zc = nullptr;
+    // ---- stream block state (SynchAndChanEst.py:72,83-100)
+    int count = 0;
+    int corr_obs = -1;
+    double tsr[3] = {0, 0, 0};
+    cf* d_in = nullptr;
+    int64_t in_cap = 0;
+    cf* d_edf = nullptr;                 // est_data_freq [num_ofdm_symb][Kd]
+    cf* d_pack = nullptr;                // the same rows without the deleted ones (:249-255), one contiguous copy to the host
+    int* pin_tsr = nullptr;              // [4] pinned host copy of s_tsr, written by the search kernel itself (tsr_host)
+    int* pin_tsr_dev = nullptr;          //     its device address
+    // GNU Radio sized buffers (a few symbols): a copy in the stream costs more than it moves (5-10 us of engine latency plus a
+    // 10-20 us bubble next to the kernels), so buffers up to PIN_IN_BYTES / PIN_OUT_BYTES go through pinned host memory that the kernels read and
+    // write in place over the link; the host's share is a memcpy of a few tens of KB
+    // (thresholds measured: input in place pays up to ~1 MB -- a 32-symbol buffer 0.107 -> 0.098 ms -- and loses at 4 MB, 0.21 ->
+    // 0.26-0.55 ms; output in place loses at 1.7 MB, 0.21 -> 0.275 ms)
+    static constexpr size_t PIN_IN_BYTES = size_t(1024) << 10, PIN_OUT_BYTES = size_t(256) << 10;
+    cf* pin_in = nullptr;
+    cf* pin_in_dev = nullptr;
+    cf* pin_out = nullptr;
+    cf* pin_out_dev = nullptr;
+    int* s_tsr = nullptr;                // [4]
+    cf* s_H = nullptr;                   // [2][N]   rows 0 / 1 of est_chan_freq_P
+    cf* s_htime = nullptr;               // [2][N]
+    cf* s_esf = nullptr;                 // [2][MM]
+    cf* s_eqg = nullptr;                 // [Ks]
+    cf* s_gain = nullptr;                // [Kd]
+    cf* s_ysc = nullptr;                 // [MM]
+    float* d_trial_m = nullptr;
+    int* d_trial_d = nullptr;
+    static constexpr int TRIAL_CAP = 1024;
+    double* d_partial = nullptr;
+    // ---- batch (frame) workspace
+    int64_t cap_frames = 0;
+    int* f_tsr = nullptr;
+    cf* f_H = nullptr;
+    cf* f_gain = nullptr;
+    cf* f_htime = nullptr;
+    double* f_seg_partial = nullptr;     // [n_seg][seg_slices(seg_len)] sigma partials of ofdm_demap_frames
+    int64_t cap_seg_partial = 0;
+    // ---- pilot tracking stage (ofdm_rx_set_pilots): K = cfg.num_data_bins occupied bins, n_pilots of them pilots
+    int n_pilots = 0;
+    int* p_idx = nullptr;                // [n_pilots] ascending list indices into binsP(K)
+    float* p_k = nullptr;                // [n_pilots] their signed bin offsets
+    uint16_t* p_src = nullptr;           // [K - n_pilots, rounded up to even] list index of the j-th data entry
+    cf pilot_conj = cf{1.f, 0.f};
+    float p_kbar = 0.f, p_inv_skk = 0.f;
+    cf* f_usum = nullptr;                // [n_seg][rows] pilot sums of ofdm_pilot_track_frames (read by the cfo launch)
+    int64_t cap_usum = 0;
+    int max_trials = 0;
+    int scan_block = 0;                  // > 0: the batch path's sync search is screened in blocks of this many trials
+    cf* d_scan_g = nullptr;              // [N + 2] recurrence kernel G, then {max |G|, 0}
+    int* d_seg_state = nullptr;          // [2] {first hit, segments done} of the stream block's segment-parallel search
+    unsigned* d_work = nullptr;          // [2] work queue of the batch demod launch {next chunk, workgroups done}
+    bool use_queue = true;
+    bool seg_armed = false;              // the kernel re-arms the two words itself; false after a launch that did not complete
+    int variant = 0;
+    unsigned* d_stamps = nullptr;
+    bool profiling = false;
+    static constexpr int PROF_RING = 32;       // per-call event triples: no host sync inside a timed loop
+    hipEvent_t ev[3 * PROF_RING] = {};
+    int64_t prof_calls = 0;
+};
+
+struct ofdm_fo {
+    ofdm_fo_cfg cfg{};
+    hipStream_t stream = nullptr;
+    RxDev dev{};
+    cf* d_tw = nullptr;
+    cf* d_zc = nullptr;
+    cf* d_rot = nullptr;                 // [n_fo][N]  self.cfo (SynchEstAndFO.py:192)
+    // ---- block state (SynchEstAndFO.py:197-222)
+    int count = 0;
+    int cor_obs = -1;
+    int dmax_tmp_ind = -1;
+    double tsr[OFDM_FO_MAX_SYNC][3] = {};
+    cf* d_in = nullptr;
+    int64_t in_cap = 0;
+    int* t_tsr = nullptr;                // [100][4]   device copy used by the kernels
+    cf* t_H = nullptr;                   // [100][N]
+    cf* t_htime = nullptr;               // [100][N]
+    cf* t_esf = nullptr;                 // [100][MM]
+    cf* t_gain = nullptr;                // [100][Kd]
+    cf* t_edf = nullptr;                 // [100][Kd]  est_data_freq
+    cf* d_code = nullptr;                // [dsss]     self.SC      (DSSS variant only)
+    cf* t_edfd = nullptr;                // [100][Kd/dsss] est_data_freq_d
+    int n_spread = 0;
+    cf* s_eqg = nullptr;                 // [Ks]
+    cf* s_ysc = nullptr;                 // [MM]
+    float* d_trial_m = nullptr;          // [n_fo * TRIAL_WIN]
+    int* d_trial_d = nullptr;
+    static constexpr int TRIAL_WIN = 256;
+    // ---- frame batch workspace (ofdm_fo_demod_frames)
+    int64_t cap_frames = 0;
+    int64_t cap_table = 0;               // trial-table entries
+    float* b_tm = nullptr;               // [frames][n_fo][trials] max|corr|
+    int* b_td = nullptr;                 //                        argmax lag
+    int* b_tsr = nullptr;                // [frames][100][4] {P*stride+cp, lag, int(max), live}
+    int* b_fo = nullptr;                 // [frames] dmax_tmp_ind (when the caller does not ask for it)
+    cf* b_gain = nullptr;                // [frames][100][Kd]
+    cf* b_edf = nullptr;                 // [frames][100][Kd] est_data_freq for the despreader (dsss > 0 only)
+};
+
+struct ofdm_trk {
+    ofdm_trk_cfg cfg{};
+    hipStream_t stream = nullptr;
+    RxDev dev{};
+    cf* d_tw = nullptr;
+    cf* d_zc = nullptr;
+    cf* d_in = nullptr;
+    int64_t in_cap = 0;
+    int64_t n_in = 0;
+    int* t_tsr = nullptr;                // [rows_sync][4]
+    cf* t_H = nullptr;                   // [rows_sync][N]
+    cf* t_imp = nullptr;                 // [rows_sync][N]
+    cf* t_esf = nullptr;                 // [rows_sync][Ks]
+    cf* t_gain = nullptr;                // [rows_sync][Kd]
+    cf* t_edf = nullptr;                 // [rows_data][Kd]
+    cf* s_ysc = nullptr;                 // [Ks]
+    float* d_trial_m = nullptr;
+    int* d_trial_d = nullptr;
+    static constexpr int TRIAL_CAP = 4096;
+};
+
+struct ofdm_tx {
+    ofdm_tx_cfg cfg{};
+    hipStream_t stream = nullptr;
+    TxDev dev{};
+    cf* d_tw = nullptr;
+    cf* d_zc = nullptr;
+    // decomposed stages
+    cf* d_sync_time = nullptr;           // [S][L] the sync symbol(s) SynchDataMux inserts, synthesised once at creation
+    int* d_pilots = nullptr;             // ascending list indices into binsP(Kd + n_pilots)
+    int n_pilots = 0;
+    cf pilot_value = cf{1.f, 0.f};
+};
+
+namespace {
+
+template <class H>
+hipStream_t pick_stream(const H* h, void* stream) { return stream ? static_cast<hipStream_t>(stream) : h->stream; }
+
+// a create that failed half way: destroy what exists, keep the text of the failure
+template <class H>
+int create_failed(H* h, int rc, int (*destroy)(H*)) {
+    const std::string keep = ofdm_last_error();
+    destroy(h);
+    return fail(rc, "%s", keep.c_str());
+}
+
+template <class T>
+int dev_alloc(T** p, size_t count) {
+    *p = nullptr;
+    if (count == 0) return OFDM_OK;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
+    if (e != hipSuccess) return fail(OFDM_ERR_NOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    return OFDM_OK;
+}
+
+// allocate-and-clear / allocate-and-copy: every size is written once.  `what` is the text of a failed fill; it is given the
+// runtime's error string.
+constexpr const char* INIT_FAILED = "device table initialisation failed: %s";
+template <class T>
+int alloc_zeroed(T** p, size_t count, const char* what = INIT_FAILED) {
+    const int rc = dev_alloc(p, count);
+    if (rc != OFDM_OK || count == 0) return rc;
+    const hipError_t e = hipMemset(*p, 0, count * sizeof(T));
+    return e == hipSuccess ? OFDM_OK : fail(OFDM_ERR_HIP, what, hipGetErrorString(e));
+}
+template <class T>
+int upload(T** p, const T* src, size_t count, const char* what = INIT_FAILED) {
+    const int rc = dev_alloc(p, count);
+    if (rc != OFDM_OK || count == 0) return rc;
+    const hipError_t e = hipMemcpy(*p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    return e == hipSuccess ? OFDM_OK : fail(OFDM_ERR_HIP, what, hipGetErrorString(e));
+}
+template <class T>
+int upload(T** p, const std::vector<T>& src, const char* what = INIT_FAILED) { return upload(p, src.data(), src.size(), what); }
+
+// frees and nulls
+template <class... T>
+void free_dev(T**... p) { ((*p ? (void)hipFree(*p) : (void)0, *p = nullptr), ...); }
+
+// a workspace that must grow cannot do so inside a stream capture (growing synchronises and allocates)
+int refuse_growth_in_capture(hipStream_t s, const char* who, const char* reserve_name) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(OFDM_ERR_INVALID, "%s: workspace must grow, which cannot happen inside a capture (call %s first)", who, reserve_name);
+    return OFDM_OK;
+}
+
+// input buffer of a stream block: grown with a quarter of headroom, after the work queued on `s` has drained
+int grow_input(cf** d_in, int64_t* in_cap, int64_t n_in, hipStream_t s) {
+    if (n_in <= *in_cap) return OFDM_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    free_dev(d_in);
+    *in_cap = 0;
+    const int64_t cap = n_in + n_in / 4 + 1024;
+    const int rc = dev_alloc(d_in, size_t(cap));
+    if (rc == OFDM_OK) *in_cap = cap;
+    return rc;
+}
+
+// Trials a work() call evaluates on n_in samples: trial P iff S*L + P*stride + N + cp < n_in (SynchAndChanEst.py:144,
+// SynchEstAndFO.py:249) and P < round(n_in/stride) (:139,143 / FO:246).
+int64_t valid_trials(const RxDev& d, int64_t n_in) {
+    const int64_t n_trials = int64_t(std::nearbyint(double(n_in) / double(d.stride)));
+    const int64_t lim = n_in - (int64_t(d.S) * d.L + d.nfft + d.cp);    // P*stride < lim
+    const int64_t p_valid = lim > 0 ? (lim + d.stride - 1) / d.stride : 0;
+    return std::min(p_valid, n_trials);
+}
+
+// mode-1 search over one host-fed buffer: max|corr| and its lag of trials p_begin .. p_begin+cnt-1 into the trial table
+SyncArgs trial_window_args(const cf* iq, int64_t n_in, int64_t p_begin, int cnt, float* trial_m, int* trial_d) {
+    SyncArgs sa{};
+    sa.iq = iq;
+    sa.frame_stride = n_in;
+    sa.frame_len = n_in;
+    sa.n_frames = 1;
+    sa.mode = 1;
+    sa.p_begin = int(p_begin);
+    sa.p_count = cnt;
+    sa.trial_m = trial_m;
+    sa.trial_d = trial_d;
+    return sa;
+}
+
+// what ofdm_rx_demod_frames and the calls that run stages behind it check about the batch and the hard bits; "" = fine
+const char* demod_bad_args(const RxDev& d, int64_t n_frames, int64_t n_dsym, const uint8_t* d_bits, int32_t bits_mode) {
+    if (n_frames > INT32_MAX / 8 || n_dsym > INT32_MAX / 8) return "batch too large";
+    if (d_bits) {
+        if (bits_mode != OFDM_BITS_PACKED && bits_mode != OFDM_BITS_UNPACKED)
+            return "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        if (bits_mode == OFDM_BITS_PACKED && ((d.Kd & 3) || (d.bps & 1)))
+            return "packed bits need num_data_bins % 4 == 0 and an even number of bits per symbol";
+    }
+    return "";
+}
+
+// ---- configuration checks the creates share (each sets the error text itself)
+int check_nfft(int n) {
+    if (n == 64 || n == 128 || n == 256 || n == 512 || n == 1024 || n == 2048 || n == 4096) return OFDM_OK;
+    return fail(OFDM_ERR_INVALID, "nfft=%d unsupported (64,128,...,4096)", n);
+}
+int check_bins(int nfft, int Ks, int Kd) {
+    if (Ks < 2 || Ks > nfft || (Ks & 1)) return fail(OFDM_ERR_INVALID, "num_synch_bins=%d must be even and in [2, nfft]", Ks);
+    if (Kd < 2 || Kd > nfft || (Kd & 1)) return fail(OFDM_ERR_INVALID, "num_data_bins=%d must be even and in [2, nfft]", Kd);
+    return OFDM_OK;
+}
+int check_pattern(int S, int D, int num_ofdm_symb) {
+    if (S < 1 || D < 1) return fail(OFDM_ERR_INVALID, "synch_dat must be [>=1, >=1]");
+    if (num_ofdm_symb < 1) return fail(OFDM_ERR_INVALID, "num_ofdm_symb must be >= 1");
+    return OFDM_OK;
+}
+
+// ---- TBCC argument checks shared by the encoders (capi_tx.hip) and the decoders (capi_rx_stages.hip); "" = fine
+constexpr int64_t TBCC_MAX_BLOCKS = (int64_t(1) << 31) - 1;   // one workgroup per block: the grid's x range
+constexpr int64_t TBCC_MAX_ITEMS = int64_t(1) << 40;          // n_seg * seg_stride (floats) and n_seg * seg_bits
+bool tbcc_bits_mode_ok(int32_t m) { return m == OFDM_BITS_PACKED || m == OFDM_BITS_UNPACKED; }
+bool tbcc_items_ok(int64_t n_seg, int64_t per_seg) { return per_seg <= TBCC_MAX_ITEMS && (n_seg <= 0 || per_seg <= TBCC_MAX_ITEMS / n_seg); }
+const char* tbcc_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K) {
+    if (!tbcc_valid_k(K)) return "K must be a multiple of 8 with 24 <= K <= 2048";
+    if (n_seg < 0 || blocks_per_seg < 0) return "negative count";
+    if (blocks_per_seg > TBCC_MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS / blocks_per_seg))
+        return "batch beyond the kernels' index range";
+    return "";
+}
+// the same with rate matching (TS 36.212 5.1.4.2): E coded bits per block
+const char* tbcc_rm_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K, int64_t E) {
+    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
+    if (*bad) return bad;
+    if (!tbcc_valid_e(K, E)) return "E must lie in 1 .. 48K";
+    return "";
+}
+
+}  // namespace

@@ -128,7 +128,7 @@ void run_all(Run& r) {
     r.variant("pack4_c", k_pack4<MOD, false>, n / 4, nb, false);
     r.variant("pack2_asm", k_pack2<MOD, true>, n / 2, nb, false);
     r.variant("pack2_c", k_pack2<MOD, false>, n / 2, nb, false);
-    if constexpr (MOD % 2 == 0) {                      // packed bytes: MOD even only (capi.hip refuses BPSK packed)
+    if constexpr (MOD % 2 == 0) {                      // packed bytes: MOD even only (capi_internal.hpp: demod_bad_args refuses BPSK packed)
         r.variant("store_p_asm", k_store_packed<MOD, true>, n / 4, nb / 8, true);
         r.variant("store_p_c", k_store_packed<MOD, false>, n / 4, nb / 8, true);
     }

@@ -220,3 +220,38 @@ def test_stream_block_uses_the_screened_search_with_the_same_outcome(om, N, cp, 
             for k in ("chan_freq", "chan_time", "synch_freq", "eq_gain"):
                 assert relerr(a[k], b[k]) < 2e-6, (i, row, k)
     assert n_det >= 3
+
+
+def test_stream_block_screened_search_then_host_loop_b_raises_the_same_index_error(om):
+    """The middle path of `work()`: the screened search runs, but the host takes the decisions after it (Loop B, packing)
+    because the estimate arrays are too short for the one-synchronisation path.  N=64, cp=16, (1, 3), num_ofdm_symb=8 and one
+    12-symbol buffer with the sync at lead L+7: three patterns need rows up to 10 of 8, so the reference raises IndexError from
+    Loop B (checked on the oracle at this very shape) after the search has updated the state.  A screened and an exhaustive
+    engine must return OFDM_ERR_INDEX with the same message, the same report and the same state rows (2e-6, the bound
+    between the two searches used throughout this file)."""
+    from ofdm_mi355x import _lib
+    N, cp, Kd, rows, n_sym = 64, 16, 60, 8, 12
+    L = N + cp
+    _, iq = _frames_with_leads(N, cp, Kd, n_sym, [L + 7], 0.02, seed=5)
+    x = iq[0][:n_sym * L].copy()
+    with pytest.raises(IndexError):
+        orc.RxOracle(rows, N, cp, N - 2, [1, 3], Kd, 100, 0.7, force_fp64=True).work(x, np.zeros(len(x), np.complex64))
+    scr = om.RxEngine(rows, N, cp, N - 2, (1, 3), Kd, 100, 0.7)
+    exh = om.RxEngine(rows, N, cp, N - 2, (1, 3), Kd, 100, 0.7)
+    assert scr.set_sync_search(False) is True and exh.set_sync_search(True) is False
+    msgs = []
+    for eng in (scr, exh):
+        assert eng.work(x, np.zeros(len(x), np.complex64)) == _lib.OFDM_ERR_INDEX
+        msgs.append(_lib.last_error())
+    assert msgs[0] == msgs[1] and "est_data_freq has 8 rows" in msgs[0], msgs
+    rs, rx_ = scr.report, exh.report
+    for fld in ("detected", "trials_run", "count", "corr_obs", "n_data_items"):
+        assert getattr(rs, fld) == getattr(rx_, fld), fld
+    assert rs.detected == 1 and rs.count == 0 and rs.corr_obs == 0
+    assert list(rs.time_synch_ref) == list(rx_.time_synch_ref)
+    for row in (0, 1):
+        a, b = scr.state(row), exh.state(row)
+        for k in ("chan_freq", "chan_time", "synch_freq", "eq_gain", "data_freq"):
+            assert np.array_equal(np.isfinite(a[k]), np.isfinite(b[k])), (row, k)
+            ok = np.isfinite(a[k])
+            assert relerr(a[k][ok], b[k][ok]) < 2e-6, (row, k)
