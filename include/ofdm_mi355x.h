@@ -401,6 +401,65 @@ int ofdm_tbcc_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg,
 int ofdm_tbcc_decode_rm_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
                                int32_t K, int32_t E, const ofdm_tbcc_out* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ CRC and scrambling (LTE)
+ * The bit-level stages around the code above, TS 36.212 5.1.1 and TS 36.211 7.2, which close the chain on the device:
+ *   transmit: payload -> ofdm_tx_crc_attach_frames -> ofdm_tx_tbcc_encode(_rm)_frames -> ofdm_tx_scramble_frames ->
+ *             ofdm_tx_modulate_frames;
+ *   receive:  LLRs -> ofdm_descramble_llr_frames -> ofdm_tbcc_decode(_rm)_frames -> ofdm_crc_check_frames -> one ok byte and
+ *             one syndrome word per block.
+ * An extension like the code itself: this text is the contract.
+ * CRC: generators gCRC24A = 0x1864CFB, gCRC24B = 0x1800063 (L = 24), gCRC16 = 0x11021 (L = 16), gCRC8 = 0x19B (L = 8), bit L on
+ *   top.  Systematic: with the payload a_0 .. a_{A-1} and the parity p_0 .. p_{L-1}, the polynomial a_0 D^{A+L-1} + .. + a_{A-1} D^L
+ *   + p_0 D^{L-1} + .. + p_{L-1} is divisible by g; the register starts at zero, nothing is reflected, there is no final XOR.
+ *   A block is the A payload bits followed by L parity bits, K = A + L; A is a multiple of 8 with 8 <= A <= 2040 and K <= 2048.
+ *   The parity read as an L-bit integer (p_0 the most significant bit) is XORed with a mask of L bits -- for PDCCH the RNTI
+ *   (x_rnti,0 = MSB, 5.3.3.2), for PBCH the antenna mask.  The mask is the scalar `mask`, or with d_mask != NULL one uint32 per
+ *   block on the device (the scalar is then not used).  A scalar mask in use with bits at or above L is OFDM_ERR_INVALID; in a
+ *   device mask those bits are ignored.
+ *   Bit layouts are those of the TBCC calls: OFDM_BITS_PACKED is MSB-first, OFDM_BITS_UNPACKED is one bit per byte of which only
+ *   bit 0 is read; written bytes are 0 or 1.  Blocks are dense: [n_blocks][K] or [n_blocks][K/8], what
+ *   ofdm_tx_tbcc_encode(_rm)_frames reads and the decoders write.
+ * Scrambling: c(n) = x1(n + 1600) ^ x2(n + 1600), x1(n + 31) = x1(n + 3) ^ x1(n) with x1(0) = 1 and x1(1 .. 30) = 0,
+ *   x2(n + 31) = x2(n + 3) ^ x2(n + 2) ^ x2(n + 1) ^ x2(n) with x2(i) = bit i of c_init, i < 31.  One sequence per segment, from
+ *   the segment's bit 0; c_init of segment s is d_cinit[s] on the device (bit 31 is ignored, 0 is allowed), so that no per-call
+ *   host work depends on it.  0 <= seg_bits < 2^31 - 1600.
+ * All device calls: asynchronous on `stream` (NULL = the handle's stream), one launch, no allocation, deterministic (no
+ * atomics).  Argument errors return OFDM_ERR_INVALID before anything is enqueued; zero counts are a no-op returning OFDM_OK. */
+typedef enum ofdm_crc_kind { OFDM_CRC24A = 0, OFDM_CRC24B = 1, OFDM_CRC16 = 2, OFDM_CRC8 = 3 } ofdm_crc_kind;
+/* L of a kind: 24 / 24 / 16 / 8.  Host arithmetic; OFDM_ERR_INVALID for an unknown kind. */
+int32_t ofdm_crc_bits(int32_t kind);
+/* *crc = the parity of the A payload bits at host_bits_packed (MSB-first), unmasked.  Host arithmetic through the kernels' own
+ * remainder routine; no device. */
+int ofdm_crc_compute(int32_t kind, const uint8_t* host_bits_packed, int32_t A, uint32_t* crc);
+/* d_payload dense [n_blocks][A] (or [A/8]) -> d_info dense [n_blocks][K] (or [K/8]): the payload, then parity ^ mask. */
+int ofdm_tx_crc_attach_frames(ofdm_tx* h, const uint8_t* d_payload, int32_t payload_mode, int64_t n_blocks, int32_t A,
+                              int32_t kind, uint32_t mask, const uint32_t* d_mask, uint8_t* d_info, int32_t info_mode, void* stream);
+typedef struct ofdm_crc_out {    /* DEVICE pointers; NULL = not wanted */
+    uint8_t*  ok;            /* [n_blocks] 1 iff syndrome == the block's mask                                                   */
+    uint32_t* syndrome;      /* [n_blocks] CRC(first A bits) ^ received parity: a host that does not know the RNTI reads it here */
+    uint8_t*  payload;       /* the first A bits of each block, dense [n_blocks][A] or [n_blocks][A/8]                          */
+    int32_t   payload_mode;  /* ofdm_bits_mode of payload                                                                       */
+} ofdm_crc_out;
+/* d_info dense [n_blocks][K] (or [K/8]) as the decoders write it.  An `out` without any pointer is a no-op. */
+int ofdm_crc_check_frames(ofdm_rx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_blocks, int32_t A, int32_t kind,
+                          uint32_t mask, const uint32_t* d_mask, const ofdm_crc_out* out, void* stream);
+/* host_out[i] = c(first + i), i < n, one bit per byte, for this c_init.  Host arithmetic through the kernels' own jump tables
+ * (random access: no stepping from 0); OFDM_ERR_INVALID for a negative count or first + n > 2^31 - 1600. */
+int ofdm_gold_bits(uint32_t c_init, int64_t first, int64_t n, uint8_t* host_out);
+/* d_out bit = d_in bit ^ c, segment s = seg_bits bits at byte s*seg_bytes of both buffers, seg_bytes = seg_bits (one bit per
+ * byte; written bytes are 0 or 1) or seg_bits / 8 (packed, needs seg_bits % 8 == 0): the coded output of
+ * ofdm_tx_tbcc_encode_frames.  d_out == d_in is allowed. */
+int ofdm_tx_scramble_frames(ofdm_tx* h, const uint8_t* d_in, int32_t mode, int64_t n_seg, int64_t seg_bits,
+                            const uint32_t* d_cinit, uint8_t* d_out, void* stream);
+/* d_out[s*out_stride + n] = the bit pattern of d_llr[s*seg_stride + n] with its sign bit XORed by c(n), n < seg_bits (strides in
+ * floats, >= seg_bits): NaN payloads, +-inf, +-0 and subnormals keep every other bit, and descrambling twice is the identity.
+ * Floats between seg_bits and the stride are not touched.  d_out == d_llr is allowed with out_stride == seg_stride. */
+int ofdm_descramble_llr_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int64_t seg_bits,
+                               const uint32_t* d_cinit, float* d_out, int64_t out_stride, void* stream);
+/* Load the kernels of this block on the handle's device: call before capturing one of its calls into a hipGraph. */
+int ofdm_tx_reserve_bitproc(ofdm_tx* h);
+int ofdm_rx_reserve_bitproc(ofdm_rx* h);
+
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the
  * gr-RXOFDM receiver (root-37 ZC, stride cp-1, gate 0.4, linear SNR) plus a brute-force carrier

@@ -320,4 +320,29 @@ const char* tbcc_rm_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t 
     return "";
 }
 
+// ---- CRC and scrambling argument checks shared by capi_common.hip, capi_tx.hip and capi_rx_stages.hip; "" = fine
+const char* crc_bad_geometry(int32_t kind, int64_t A) {
+    if (kind < OFDM_CRC24A || kind > OFDM_CRC8) return "kind must be OFDM_CRC24A, OFDM_CRC24B, OFDM_CRC16 or OFDM_CRC8";
+    if (A < CRC_A_MIN || A > CRC_A_MAX || A % 8) return "A must be a multiple of 8 with 8 <= A <= 2040";
+    if (A + crc_bits(kind) > CRC_K_MAX) return "A + L must not exceed 2048";
+    return "";
+}
+const char* crc_bad_args(int32_t kind, int64_t A, int64_t n_blocks, int32_t mode_a, int32_t mode_b, uint32_t mask, const uint32_t* d_mask) {
+    const char* bad = crc_bad_geometry(kind, A);
+    if (*bad) return bad;
+    if (n_blocks < 0) return "negative count";
+    if (n_blocks > TBCC_MAX_BLOCKS) return "batch beyond the kernel's index range";
+    if (!tbcc_bits_mode_ok(mode_a) || !tbcc_bits_mode_ok(mode_b)) return "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+    if (!d_mask && (mask >> crc_bits(kind))) return "scalar mask has bits at or above L";
+    return "";
+}
+// n_seg segments of seg_bits scrambled bits at strides of stride_a / stride_b elements
+const char* gold_bad_args(int64_t n_seg, int64_t seg_bits, int64_t stride_a, int64_t stride_b) {
+    if (n_seg < 0 || seg_bits < 0) return "negative count";
+    if (seg_bits >= GOLD_MAX_BITS) return "seg_bits must be below 2^31 - 1600";
+    if (stride_a < seg_bits || stride_b < seg_bits) return "stride shorter than seg_bits";
+    if (!tbcc_items_ok(n_seg, stride_a) || !tbcc_items_ok(n_seg, stride_b)) return "batch beyond the kernel's index range";
+    return "";
+}
+
 }  // namespace

@@ -400,4 +400,58 @@ int ofdm_tbcc_decode_rm_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, in
     return OFDM_OK;
 }
 
+// ---- Gold-sequence descrambling of LLRs and the CRC check (definition: include/ofdm_mi355x.h)
+int ofdm_rx_reserve_bitproc(ofdm_rx* h) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_bitproc: null handle");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(bitproc_prepare());
+    return OFDM_OK;
+}
+
+int ofdm_descramble_llr_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int64_t seg_bits,
+                               const uint32_t* d_cinit, float* d_out, int64_t out_stride, void* stream) {
+    const char* bad = gold_bad_args(n_seg, seg_bits, seg_stride, out_stride);
+    if (!*bad && d_llr && d_out == d_llr && out_stride != seg_stride) bad = "in place needs out_stride == seg_stride";
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: %s", bad);
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: null handle");
+    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
+    if (!d_llr || !d_out || !d_cinit) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: null buffer");
+    GoldArgs a{};
+    a.in = d_llr;
+    a.out = d_out;
+    a.in_stride = seg_stride;
+    a.out_stride = out_stride;
+    a.n_seg = n_seg;
+    a.seg_bits = seg_bits;
+    a.cinit = d_cinit;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_gold_llr(a, pick_stream(h, stream)));
+    return OFDM_OK;
+}
+
+int ofdm_crc_check_frames(ofdm_rx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_blocks, int32_t A, int32_t kind,
+                          uint32_t mask, const uint32_t* d_mask, const ofdm_crc_out* out, void* stream) {
+    const bool want_payload = out && out->payload;
+    const char* bad = crc_bad_args(kind, A, n_blocks, info_mode, want_payload ? out->payload_mode : info_mode, mask, d_mask);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: %s", bad);
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: null handle");
+    if (n_blocks == 0 || !out || (!out->ok && !out->syndrome && !out->payload)) return OFDM_OK;
+    if (!d_info) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: null d_info");
+    CrcArgs a{};
+    a.kind = kind;
+    a.A = A;
+    a.n_blocks = n_blocks;
+    a.mask = mask;
+    a.mask_dev = d_mask;
+    a.info_mode = info_mode;
+    a.payload_mode = want_payload ? out->payload_mode : info_mode;
+    a.info_in = d_info;
+    a.ok = out->ok;
+    a.syndrome = out->syndrome;
+    a.payload_out = out->payload;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_crc(a, pick_stream(h, stream)));
+    return OFDM_OK;
+}
+
 }  // extern "C"

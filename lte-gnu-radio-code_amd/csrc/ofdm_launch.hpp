@@ -265,6 +265,42 @@ hipError_t launch_tbcc_decode_rm(const TbccDecRmArgs& a, hipStream_t s);
 hipError_t tbcc_decode_prepare();
 size_t tbcc_lds_bytes(int K);            // survivor memory of one block: 8 B per trellis step, rounded up to 32 steps
 
+// ---- CRC and Gold-sequence scrambling (bitproc.hip; contract: include/ofdm_mi355x.h)
+constexpr int GOLD_CH = 1024;            // sequence bits one lane produces after its jump
+constexpr int GOLD_LEVELS = 21;          // jump tables M^(GOLD_CH * 2^k), k < 21: every bit index below 2^31
+constexpr int GOLD_SPAN = 64 * GOLD_CH;  // bits of a segment one workgroup (one wave) owns
+constexpr int64_t GOLD_MAX_BITS = (int64_t(1) << 31) - 1600;   // seg_bits < this: n + 1600 stays below 2^31
+struct GoldArgs {
+    const void* in;          // LLR: float [n_seg][in_stride]; bits: uint8 [n_seg][in_stride] (one per byte, or packed MSB-first)
+    void* out;               // the same layout at out_stride; out == in (equal strides) is allowed
+    int64_t in_stride, out_stride;       // elements: floats or bytes
+    int64_t n_seg, seg_bits;
+    const uint32_t* cinit;   // [n_seg]
+};
+constexpr int CRC_A_MIN = 8, CRC_A_MAX = 2040, CRC_K_MAX = 2048;
+struct CrcArgs {
+    int kind, A;             // ofdm_crc_kind, payload bits
+    int64_t n_blocks;
+    uint32_t mask;           // XORed into the parity (p0 = MSB), used when mask_dev is null
+    const uint32_t* mask_dev;            // [n_blocks], or null
+    int info_mode, payload_mode;         // ofdm_bits_mode
+    // attach (info_out != null): payload_in dense [n_blocks][A] -> info_out dense [n_blocks][A + L]
+    const uint8_t* payload_in;
+    uint8_t* info_out;
+    // check: info_in dense [n_blocks][A + L] -> each of the outputs that is not null
+    const uint8_t* info_in;
+    uint8_t* ok;             // [n_blocks]
+    uint32_t* syndrome;      // [n_blocks]
+    uint8_t* payload_out;    // dense [n_blocks][A]
+};
+hipError_t launch_gold_llr(const GoldArgs& a, hipStream_t s);
+hipError_t launch_gold_bits(const GoldArgs& a, int packed, hipStream_t s);
+hipError_t launch_crc(const CrcArgs& a, hipStream_t s);
+hipError_t bitproc_prepare();            // loads the kernels' code objects (before a stream capture)
+int crc_bits(int kind);                  // 24 / 24 / 16 / 8, 0 for an unknown kind
+uint32_t crc_host(int kind, const uint8_t* bits_packed, int A);            // the kernels' remainder routine on the host
+void gold_bits_host(uint32_t c_init, int64_t first, int64_t n, uint8_t* out);   // c(first ..) from the kernels' jump tables
+
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
 // batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs

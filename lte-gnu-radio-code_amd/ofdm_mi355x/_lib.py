@@ -23,6 +23,7 @@ COMPAT_UTSA = 0
 COMPAT_RXOFDM = 1
 BITS_NONE, BITS_PACKED, BITS_UNPACKED = 0, 1, 2
 PILOT_CPE, PILOT_CPE_SLOPE = 0, 1
+CRC24A, CRC24B, CRC16, CRC8 = 0, 1, 2, 3
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -87,6 +88,11 @@ class TbccOut(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("metric", C.c_void_p), ("tb_ok", C.c_void_p)]
 
 
+class CrcOut(C.Structure):
+    """ofdm_crc_out: device pointers of the CRC check (None = not wanted)."""
+    _fields_ = [("ok", C.c_void_p), ("syndrome", C.c_void_p), ("payload", C.c_void_p), ("payload_mode", C.c_int32)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -145,6 +151,19 @@ PROTOTYPES = {
                                                 C.c_void_p, C.c_int64, C.c_void_p]),
     "ofdm_tbcc_decode_rm_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                              C.POINTER(TbccOut), C.c_void_p]),
+    "ofdm_crc_bits": (C.c_int32, [C.c_int32]),
+    "ofdm_crc_compute": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]),
+    "ofdm_tx_crc_attach_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ofdm_crc_check_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
+                                        C.POINTER(CrcOut), C.c_void_p]),
+    "ofdm_gold_bits": (C.c_int, [C.c_uint32, C.c_int64, C.c_int64, C.c_void_p]),
+    "ofdm_tx_scramble_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "ofdm_descramble_llr_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p]),
+    "ofdm_tx_reserve_bitproc": (C.c_int, [C.c_void_p]),
+    "ofdm_rx_reserve_bitproc": (C.c_int, [C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

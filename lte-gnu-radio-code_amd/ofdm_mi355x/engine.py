@@ -89,6 +89,29 @@ def tbcc_rm_blocks(seg_bits: int, K: int, E: int) -> int:
     return int(check(_lib.load().ofdm_tbcc_rm_blocks(int(seg_bits), int(K), int(E))))
 
 
+def crc_bits(kind: int) -> int:
+    """ofdm_crc_bits: the parity bits L of a CRC kind (CRC24A, CRC24B: 24, CRC16: 16, CRC8: 8)."""
+    return int(check(_lib.load().ofdm_crc_bits(int(kind))))
+
+
+def crc_compute(kind: int, bits_packed, A: int | None = None) -> int:
+    """ofdm_crc_compute: the unmasked parity (an L-bit integer, p0 on top) of A payload bits packed MSB-first; host arithmetic."""
+    buf = np.ascontiguousarray(bits_packed, dtype=np.uint8)
+    A = 8 * buf.size if A is None else int(A)
+    if A > 8 * buf.size:
+        raise ValueError("crc_compute: A = %d bits from %d bytes" % (A, buf.size))
+    crc = C.c_uint32(0)
+    check(_lib.load().ofdm_crc_compute(int(kind), ptr(buf), A, C.byref(crc)))
+    return int(crc.value)
+
+
+def gold_bits(c_init: int, first: int, n: int) -> np.ndarray:
+    """ofdm_gold_bits: c(first .. first + n - 1) of TS 36.211 7.2 for c_init, one bit per byte; host arithmetic, random access."""
+    out = np.empty(max(int(n), 0), np.uint8)
+    check(_lib.load().ofdm_gold_bits(int(c_init) & 0xFFFFFFFF, int(first), int(n), ptr(out)))
+    return out
+
+
 class RxEngine:
     """Receive chain handle (sync search, LS channel estimate, FFT + equalise, de-map)."""
 
@@ -269,6 +292,29 @@ class RxEngine:
         out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
         check(self.lib.ofdm_tbcc_decode_rm_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                   int(E), C.byref(out), ptr(stream)))
+
+    # ---- Gold-sequence descrambling in front of the decoder, CRC check behind it (TS 36.211 7.2, TS 36.212 5.1.1) ----
+    def reserve_bitproc(self):
+        """Loads the descrambling and CRC kernels (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_bitproc(self._h))
+
+    def descramble_llr_frames(self, d_llr, n_seg, seg_stride, seg_bits, d_cinit, d_out, out_stride=None, stream=None):
+        """ofdm_descramble_llr_frames: the sign bit of float n of segment s is XORed with c(n) of c_init = d_cinit[s] (device
+        uint32); strides in floats, d_out may be d_llr at the same stride."""
+        check(self.lib.ofdm_descramble_llr_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(seg_bits), ptr(d_cinit),
+                                                  ptr(d_out), int(seg_stride if out_stride is None else out_stride), ptr(stream)))
+
+    def crc_check_frames(self, d_info, n_blocks, A, kind, mask=0, d_mask=None, info_mode=BITS_UNPACKED, d_ok=None, d_syndrome=None,
+                         d_payload=None, payload_mode=BITS_UNPACKED, stream=None):
+        """ofdm_crc_check_frames: d_info dense [n_blocks][A + L] bits as the decoders write them -> ok uint8 (syndrome == mask),
+        syndrome uint32 (CRC of the first A bits ^ the received parity), payload dense [n_blocks][A]; mask: the scalar, or
+        d_mask one device uint32 per block."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.CrcOut(addr(d_ok), addr(d_syndrome), addr(d_payload), int(payload_mode))
+        check(self.lib.ofdm_crc_check_frames(self._h, ptr(d_info), int(info_mode), int(n_blocks), int(A), int(kind), int(mask),
+                                             ptr(d_mask), C.byref(out), ptr(stream)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -465,6 +511,24 @@ class TxEngine:
         TS 36.212 5.1.4.2: E coded bits per block from bit 0 of the segment, then zeros."""
         check(self.lib.ofdm_tx_tbcc_encode_rm_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
                                                      int(E), ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
+
+    # ---- CRC attach in front of the encoder, Gold-sequence scrambling behind it (TS 36.212 5.1.1, TS 36.211 7.2) ----
+    def reserve_bitproc(self):
+        """Loads the CRC and scrambling kernels (before a graph capture)."""
+        check(self.lib.ofdm_tx_reserve_bitproc(self._h))
+
+    def crc_attach_frames(self, d_payload, n_blocks, A, kind, d_info, mask=0, d_mask=None, payload_mode=BITS_UNPACKED,
+                          info_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_crc_attach_frames: d_payload dense [n_blocks][A] bits -> d_info dense [n_blocks][A + L]: the payload, then the
+        parity XORed with the mask (the scalar, or d_mask one device uint32 per block); what tbcc_encode(_rm)_frames reads."""
+        check(self.lib.ofdm_tx_crc_attach_frames(self._h, ptr(d_payload), int(payload_mode), int(n_blocks), int(A), int(kind),
+                                                 int(mask), ptr(d_mask), ptr(d_info), int(info_mode), ptr(stream)))
+
+    def scramble_frames(self, d_in, n_seg, seg_bits, d_cinit, d_out, mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_scramble_frames: bit n of segment s ^ c(n) of c_init = d_cinit[s] (device uint32), in the segment layout of
+        tbcc_encode_frames' coded output; d_out may be d_in."""
+        check(self.lib.ofdm_tx_scramble_frames(self._h, ptr(d_in), int(mode), int(n_seg), int(seg_bits), ptr(d_cinit), ptr(d_out),
+                                               ptr(stream)))
 
     # ---- decomposed stages (device buffers)
     def random_bits(self, seed, offset, d_bits, n_bits, stream=None):
