@@ -460,6 +460,73 @@ int ofdm_descramble_llr_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, in
 int ofdm_tx_reserve_bitproc(ofdm_tx* h);
 int ofdm_rx_reserve_bitproc(ofdm_rx* h);
 
+/* ------------------------------------------------------------------------------------------ channel code (LTE turbo)
+ * The rate-1/3 turbo code of TS 36.212 5.1.3.2 -- two 8-state constituent encoders around a QPP interleaver, with trellis
+ * termination -- on the frame-batched path: the data channel's code next to the TBCC above, with an iterative max-log-MAP
+ * decoder.  An extension like the TBCC: the reference has no channel code, so this text is the contract.  Rate matching
+ * (5.1.4.1), code-block segmentation and the table of 3GPP (f1, f2) pairs are not part of it.
+ * Code block: K information bits c[0..K), K a multiple of 8 with 40 <= K <= 6144 (LTE's 188 sizes are a subset).
+ * Interleaver: pi(i) = (f1 i + f2 i^2) mod K with 0 <= f1, f2 < K, handed over by the caller.  A call whose (K, f1, f2) is not a
+ *   permutation of 0 .. K-1 returns OFDM_ERR_INVALID before anything is enqueued (O(K) host work per call).
+ * Constituent encoder: feedback 1 + D^2 + D^3, parity 1 + D + D^3; state s = 4 r1 + 2 r2 + r3 with r1 the most recent, start
+ *   state 0.  Input u gives a = u ^ r2 ^ r3, parity z = a ^ r1 ^ r3, next(s, u) = 4 a + (s >> 1).  Encoder 1 runs over c[k] and
+ *   gives z[k]; encoder 2 runs over c[pi(i)] and gives z'[i].  Termination, three steps per encoder: u = r2 ^ r3 (so a = 0),
+ *   transmitted x = u and z = r1 ^ r3; x_K .. x_{K+2}, z_K .. z_{K+2} from encoder 1, x'_K .. , z'_K .. from encoder 2.
+ * Streams of K + 4 bits (5.1.3.2.2):   k < K: d0 = c[k], d1 = z[k], d2 = z'[k];
+ *   k = K:   x_K, z_K, x_{K+1};   K+1: z_{K+1}, x_{K+2}, z_{K+2};   K+2: x'_K, z'_K, x'_{K+1};   K+3: z'_{K+1}, x'_{K+2}, z'_{K+2}.
+ *   Coded order as in the TBCC calls, e[3k+j] = dj[k]: 3K + 12 bits per block, the 12 tail values at 3K .. 3K+11 as
+ *   x_K z_K x_{K+1} z_{K+1} x_{K+2} z_{K+2} followed by the same six primed.
+ * Segments: the TBCC rules with 3K + 12 in place of 3K -- blocks back to back from bit 0 of the segment, filler zeros behind
+ *   them (written by the encoder, ignored by the decoder).  3K + 12 is no multiple of 8: packed blocks may start inside a byte.
+ * Decoder: max-log-MAP, n_iter full iterations (1 <= n_iter <= 16), fully determined; every operation is one IEEE float32
+ *   operation in the order written.  Positive LLRs favour bit 0; an input LLR that is not finite counts as 0; sigma(0) = +1,
+ *   sigma(1) = -1.  max(a, b) is the larger value; which zero a max of +0 and -0 returns is not specified (no comparison,
+ *   decision or non-zero value depends on it).
+ *   SISO(ls, la, lp, t[0..6)) -> (post, ext), metrics twice the log-domain ones:
+ *     x_k = ls_k + la_k;  gamma_k(u, z) = sigma(u) x_k + sigma(z) lp_k  (exact products, one add).
+ *     Forward: A_0 = (0, -inf, .., -inf); k = 0 .. K-1: m(s') = max over the two branches (s, u) -> s' of A_k(s) + gamma_k(u, z);
+ *       A_{k+1}(s') = m(s') - m(0) if (k+1) mod 8 == 0, else m(s').
+ *     Tail: from state s follow s_0 = s, s_{j+1} = s_j >> 1; with the bits of s_j, g_j = sigma(r2^r3) t[2j] + sigma(r1^r3) t[2j+1];
+ *       b(s) = (g_0 + g_1) + g_2;  B_K(s) = b(s) - b(0).
+ *     Backward, k = K-1 .. 0: t_u(s) = (A_k(s) + gamma_k(u, z)) + B_{k+1}(next(s, u));  M_u = max_s t_u(s);
+ *       post_k = 0.5 (M_0 - M_1);  ext_k = 0.75 (post_k - x_k);  n(s) = max_u (gamma_k(u, z) + B_{k+1}(next(s, u)));
+ *       B_k(s) = n(s) - n(0) if k mod 8 == 0, else n(s).
+ *     State 0 is always reachable, so every subtrahend is finite and finite inputs give no NaN; finite LLRs whose sums overflow
+ *     are outside the contract.
+ *   With ls[k] = l[3k], lp1[k] = l[3k+1], lp2[k] = l[3k+2], tail 1 = l[3K .. 3K+5], tail 2 = l[3K+6 .. 3K+11] of the block's
+ *   3K + 12 LLRs l (each made 0 where it is not finite):  la1 = 0;  per iteration  (., e1) = SISO(ls, la1, lp1, tail 1);
+ *   ls2[i] = ls[pi(i)], la2[i] = e1[pi(i)];  (post2, e2) = SISO(ls2, la2, lp2, tail 2);  la1[pi(i)] = e2[i].
+ *   Outputs per block: llr[pi(i)] = post2[i] of the last iteration; bit[k] = (llr[k] < 0), so that +0 and -0 both decide 0.
+ * Deterministic: a block's outputs depend on its own 3K + 12 LLRs only -- the same bits and llr alone, in any batch, at any
+ * stride and on every call (no atomics). */
+/* floor(seg_bits / (3K + 12)): the blocks a segment can carry.  Host arithmetic; OFDM_ERR_INVALID for a bad K or seg_bits < 0. */
+int64_t ofdm_turbo_blocks(int64_t seg_bits, int32_t K);
+/* OFDM_OK iff K is valid, 0 <= f1, f2 < K and pi is a permutation of 0 .. K-1.  Host arithmetic, O(K). */
+int ofdm_turbo_qpp_check(int32_t K, int32_t f1, int32_t f2);
+/* The layouts, filler, no-op and error rules of ofdm_tx_tbcc_encode_frames with 3K + 12 coded bits per block
+ * (seg_bits >= blocks_per_seg*(3K+12)); a triple that is no permutation is OFDM_ERR_INVALID.  One launch, no allocation. */
+int ofdm_tx_turbo_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                int32_t K, int32_t f1, int32_t f2, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits,
+                                void* stream);
+typedef struct ofdm_turbo_out {  /* DEVICE pointers; NULL = not wanted */
+    uint8_t* bits;       /* dense [n_seg][blocks_per_seg][K] decoded bits: packed MSB-first (K/8 bytes per block) or one per byte */
+    int32_t  bits_mode;  /* ofdm_bits_mode of bits                                                                             */
+    float*   llr;        /* dense [n_seg][blocks_per_seg][K] float32 a-posteriori LLRs                                         */
+} ofdm_turbo_out;
+/* Sizes the handle's device workspace for decoding up to n_blocks blocks of K bits per call and loads the kernel.  Workspace:
+ * 4 n_blocks K bytes of extrinsic values plus 256 ceil(n_blocks / 8) ceil(K / 32) bytes of forward metrics (one checkpoint of
+ * 8 states x 8 blocks every 32 trellis steps); it only grows.  Growing waits for the device and allocates, so call this before
+ * capturing ofdm_turbo_decode_frames into a hipGraph: inside a capture a call that would have to grow returns OFDM_ERR_INVALID. */
+int ofdm_rx_reserve_turbo(ofdm_rx* h, int64_t n_blocks, int32_t K);
+/* Block (s, b) reads the 3K + 12 float32 LLRs at d_llr + s*seg_stride + b*(3K+12) (seg_stride in floats, >=
+ * blocks_per_seg*(3K+12)).  Asynchronous on `stream` (NULL = the handle's stream): one launch, no host synchronisation and, once
+ * reserved, no allocation.  The workspace belongs to the handle: calls on one handle must not overlap on the device (one stream,
+ * or ordered by events).  n_seg == 0, blocks_per_seg == 0 or an `out` without any pointer is a no-op returning OFDM_OK.
+ * Argument errors (NULL handle, bad K, a triple that is no permutation, n_iter outside 1 .. 16, seg_stride too short, a negative
+ * count, a batch beyond the kernel's index range) return OFDM_ERR_INVALID before anything is enqueued. */
+int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
+                             int32_t f1, int32_t f2, int32_t n_iter, const ofdm_turbo_out* out, void* stream);
+
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the
  * gr-RXOFDM receiver (root-37 ZC, stride cp-1, gate 0.4, linear SNR) plus a brute-force carrier

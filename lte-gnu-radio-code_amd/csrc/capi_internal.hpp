@@ -94,6 +94,9 @@ struct ofdm_rx {
     float p_kbar = 0.f, p_inv_skk = 0.f;
     cf* f_usum = nullptr;                // [n_seg][rows] pilot sums of ofdm_pilot_track_frames (read by the cfo launch)
     int64_t cap_usum = 0;
+    // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints
+    float* t_ws = nullptr;
+    int64_t cap_turbo = 0;               // floats
     int max_trials = 0;
     int scan_block = 0;                  // > 0: the batch path's sync search is screened in blocks of this many trials
     cf* d_scan_g = nullptr;              // [N + 2] recurrence kernel G, then {max |G|, 0}

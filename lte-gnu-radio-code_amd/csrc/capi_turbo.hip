@@ -1,0 +1,120 @@
+// capi_turbo.hip -- the LTE turbo code on the frame-batched path (definition: include/ofdm_mi355x.h): the
+// host-only block count and interleaver check, the encode call of the transmitter handle, reserve and decode of the receiver handle.
+#include "capi_internal.hpp"
+
+namespace {
+constexpr const char* TURBO_BAD_K = "K must be a multiple of 8 with 40 <= K <= 6144";
+// K, the counts and the interleaver, in the order the calls report them; "" = fine.  The permutation check is O(K) host work.
+const char* turbo_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K, int64_t f1, int64_t f2) {
+    if (!turbo_valid_k(K)) return TURBO_BAD_K;
+    if (n_seg < 0 || blocks_per_seg < 0) return "negative count";
+    if (n_seg > TBCC_MAX_BLOCKS || blocks_per_seg > TBCC_MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS / blocks_per_seg))
+        return "batch beyond the kernels' index range";
+    if (f1 < 0 || f1 >= K || f2 < 0 || f2 >= K) return "f1 and f2 must lie in 0 .. K-1";
+    if (!turbo_qpp_valid(K, f1, f2)) return "(f1 i + f2 i^2) mod K is not a permutation of 0 .. K-1";
+    return "";
+}
+bool turbo_wanted(const ofdm_turbo_out* o) { return o && (o->bits || o->llr); }
+int turbo_ensure(ofdm_rx* h, int64_t n_blocks, int32_t K, hipStream_t s) {
+    if (turbo_ws_floats(n_blocks, K) <= h->cap_turbo) return OFDM_OK;
+    const int rc = refuse_growth_in_capture(s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo");
+    return rc != OFDM_OK ? rc : ofdm_rx_reserve_turbo(h, n_blocks, K);
+}
+}  // namespace
+
+extern "C" {
+
+int64_t ofdm_turbo_blocks(int64_t seg_bits, int32_t K) {
+    if (!turbo_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_turbo_blocks: %s", TURBO_BAD_K);
+    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_turbo_blocks: negative seg_bits");
+    return seg_bits / (3 * int64_t(K) + 12);
+}
+
+int ofdm_turbo_qpp_check(int32_t K, int32_t f1, int32_t f2) {
+    const char* bad = turbo_bad_geometry(0, 0, K, f1, f2);
+    return *bad ? fail(OFDM_ERR_INVALID, "ofdm_turbo_qpp_check: %s", bad) : OFDM_OK;
+}
+
+int ofdm_tx_turbo_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                int32_t K, int32_t f1, int32_t f2, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: null handle");
+    const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
+    if (!*bad) {
+        if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_bits < blocks_per_seg * (3K + 12)";
+        else if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) bad = "packed coded bits need seg_bits % 8 == 0";
+        else if (!tbcc_items_ok(n_seg, seg_bits)) bad = "batch beyond the kernel's index range";
+    }
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: %s", bad);
+    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
+    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: null buffer");
+    TurboEncArgs a{};
+    a.info = d_info;
+    a.info_mode = info_mode;
+    a.n_seg = n_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.coded = d_coded;
+    a.coded_mode = coded_mode;
+    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    a.q = turbo_qpp(K, f1, f2);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_turbo_encode(a, pick_stream(h, stream)));
+    return OFDM_OK;
+}
+
+// Sizes the workspace for n_blocks blocks of K bits (it only grows) and loads the decoder's code object.  Growing waits for
+// the device, so it cannot happen inside a capture: ofdm_turbo_decode_frames refuses there and names this call.
+int ofdm_rx_reserve_turbo(ofdm_rx* h, int64_t n_blocks, int32_t K) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: null handle");
+    if (!turbo_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: %s", TURBO_BAD_K);
+    if (n_blocks < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: negative count");
+    if (n_blocks > TBCC_MAX_BLOCKS) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: batch beyond the kernel's index range");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(turbo_decode_prepare());
+    const int64_t need = turbo_ws_floats(n_blocks, K);
+    if (need <= h->cap_turbo) return OFDM_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipDeviceSynchronize());
+    free_dev(&h->t_ws);
+    h->cap_turbo = 0;
+    const int rc = dev_alloc(&h->t_ws, size_t(need));
+    if (rc != OFDM_OK) return rc;
+    h->cap_turbo = need;
+    return OFDM_OK;
+}
+
+int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
+                             int32_t f1, int32_t f2, int32_t n_iter, const ofdm_turbo_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_frames: null handle");
+    const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
+    if (!*bad) {
+        if (n_iter < 1 || n_iter > TURBO_ITER_MAX) bad = "n_iter must lie in 1 .. 16";
+        else if (seg_stride < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_stride < blocks_per_seg * (3K + 12)";
+        else if (!tbcc_items_ok(n_seg, seg_stride)) bad = "batch beyond the kernel's index range";
+        else if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode)) bad = "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+    }
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_frames: %s", bad);
+    if (n_seg == 0 || blocks_per_seg == 0 || !turbo_wanted(out)) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_frames: null d_llr");
+    hipStream_t s = pick_stream(h, stream);
+    const int64_t n_blocks = n_seg * blocks_per_seg;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const int rc = turbo_ensure(h, n_blocks, K, s);
+    if (rc != OFDM_OK) return rc;
+    TurboDecArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_blocks;
+    a.blocks_per_seg = blocks_per_seg;
+    a.n_iter = n_iter;
+    a.ext = h->t_ws;
+    a.ckpt = h->t_ws + n_blocks * K;
+    a.bits = out->bits;
+    a.bits_mode = out->bits_mode;
+    a.llr_out = out->llr;
+    a.q = turbo_qpp(K, f1, f2);
+    HIP_TRY(launch_turbo_decode(a, s));
+    return OFDM_OK;
+}
+
+}  // extern "C"

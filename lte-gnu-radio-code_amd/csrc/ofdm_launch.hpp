@@ -301,6 +301,47 @@ int crc_bits(int kind);                  // 24 / 24 / 16 / 8, 0 for an unknown k
 uint32_t crc_host(int kind, const uint8_t* bits_packed, int A);            // the kernels' remainder routine on the host
 void gold_bits_host(uint32_t c_init, int64_t first, int64_t n, uint8_t* out);   // c(first ..) from the kernels' jump tables
 
+// ---- LTE turbo code (turbo.hip; contract: include/ofdm_mi355x.h)
+constexpr int TURBO_K_MIN = 40, TURBO_K_MAX = 6144;
+constexpr int TURBO_ITER_MAX = 16;
+constexpr int TURBO_GROUP = 8;           // code blocks per wave of the decoder: lane = (block, state)
+constexpr int TURBO_CKPT = 32;           // trellis steps between two stored forward metrics (a multiple of 8, the normalisation grid)
+inline bool turbo_valid_k(int64_t K) { return K >= TURBO_K_MIN && K <= TURBO_K_MAX && K % 8 == 0; }
+bool turbo_qpp_valid(int64_t K, int64_t f1, int64_t f2);     // host, O(K): a valid K, 0 <= f1, f2 < K and pi a permutation
+struct TurboQpp {            // pi(i) = (f1 i + f2 i^2) mod K and the increments the kernels step it with, all reduced mod K
+    int K, f1, f2;
+    int g2;                  // 2 f2:           (pi(i+2) - pi(i+1)) - (pi(i+1) - pi(i))
+    int c8, c16, c128;       // 8 f1 + 64 f2, 16 f2, 128 f2:  pi(i+8) - pi(i) = c8 + c16 i, which grows by c128 per 8 steps
+};
+TurboQpp turbo_qpp(int K, int f1, int f2);
+struct TurboEncArgs {
+    const uint8_t* info;     // dense [n_seg][blocks_per_seg][K] bits
+    int info_mode;           // ofdm_bits_mode
+    int64_t n_seg;
+    int blocks_per_seg;
+    uint8_t* coded;          // [n_seg][seg_bytes]: blocks_per_seg*(3K+12) coded bits from bit 0, then zeros
+    int coded_mode;          // ofdm_bits_mode
+    int64_t seg_bytes;       // seg_bits (one bit per byte) or seg_bits / 8 (packed)
+    TurboQpp q;
+};
+struct TurboDecArgs {
+    const float* llr;        // block (seg, b) = 3K+12 floats at llr + seg*seg_stride + b*(3K+12)
+    int64_t seg_stride;      // floats
+    int64_t n_blocks;        // n_seg * blocks_per_seg: one wave per TURBO_GROUP of them
+    int blocks_per_seg;
+    int n_iter;
+    float* ext;              // workspace [n_blocks][K]: the extrinsic values, at the end llr in natural order
+    float* ckpt;             // workspace [waves][ceil(K / TURBO_CKPT)][64]: forward metrics at the tile starts
+    uint8_t* bits;           // dense [n_blocks][K] bits, or null
+    int bits_mode;           // ofdm_bits_mode
+    float* llr_out;          // dense [n_blocks][K], or null
+    TurboQpp q;
+};
+int64_t turbo_ws_floats(int64_t n_blocks, int K);            // ext + ckpt of a decode of n_blocks blocks, ext first
+hipError_t launch_turbo_encode(const TurboEncArgs& a, hipStream_t s);
+hipError_t launch_turbo_decode(const TurboDecArgs& a, hipStream_t s);
+hipError_t turbo_decode_prepare();       // loads the decoder's code object (before a stream capture)
+
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
 // batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs

@@ -93,6 +93,11 @@ class CrcOut(C.Structure):
     _fields_ = [("ok", C.c_void_p), ("syndrome", C.c_void_p), ("payload", C.c_void_p), ("payload_mode", C.c_int32)]
 
 
+class TurboOut(C.Structure):
+    """ofdm_turbo_out: device pointers of the turbo decoder (None = not wanted)."""
+    _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("llr", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -164,6 +169,13 @@ PROTOTYPES = {
                                              C.c_int64, C.c_void_p]),
     "ofdm_tx_reserve_bitproc": (C.c_int, [C.c_void_p]),
     "ofdm_rx_reserve_bitproc": (C.c_int, [C.c_void_p]),
+    "ofdm_turbo_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
+    "ofdm_turbo_qpp_check": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "ofdm_tx_turbo_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]),
+    "ofdm_rx_reserve_turbo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
+    "ofdm_turbo_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(TurboOut), C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

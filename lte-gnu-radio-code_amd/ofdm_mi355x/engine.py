@@ -89,6 +89,16 @@ def tbcc_rm_blocks(seg_bits: int, K: int, E: int) -> int:
     return int(check(_lib.load().ofdm_tbcc_rm_blocks(int(seg_bits), int(K), int(E))))
 
 
+def turbo_blocks(seg_bits: int, K: int) -> int:
+    """ofdm_turbo_blocks: the turbo code blocks of K information bits (3K + 12 coded bits each) a segment of seg_bits carries."""
+    return int(check(_lib.load().ofdm_turbo_blocks(int(seg_bits), int(K))))
+
+
+def turbo_qpp_check(K: int, f1: int, f2: int) -> bool:
+    """ofdm_turbo_qpp_check: True iff K is a valid block size, 0 <= f1, f2 < K and (f1 i + f2 i^2) mod K is a permutation."""
+    return _lib.load().ofdm_turbo_qpp_check(int(K), int(f1), int(f2)) == 0
+
+
 def crc_bits(kind: int) -> int:
     """ofdm_crc_bits: the parity bits L of a CRC kind (CRC24A, CRC24B: 24, CRC16: 16, CRC8: 8)."""
     return int(check(_lib.load().ofdm_crc_bits(int(kind))))
@@ -292,6 +302,23 @@ class RxEngine:
         out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
         check(self.lib.ofdm_tbcc_decode_rm_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                   int(E), C.byref(out), ptr(stream)))
+
+    # ---- LTE turbo code (TS 36.212 5.1.3.2): the iterative max-log-MAP decoder behind the same LLR buffers ----
+    def reserve_turbo(self, n_blocks: int, K: int):
+        """Sizes the decoder's workspace for up to n_blocks code blocks of K bits per call (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_turbo(self._h, int(n_blocks), int(K)))
+
+    def turbo_decode_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, f1, f2, n_iter, d_bits=None, bits_mode=BITS_UNPACKED,
+                            d_llr_out=None, stream=None):
+        """ofdm_turbo_decode_frames: block (s, b) = the 3K + 12 float32 LLRs at d_llr + s*seg_stride + b*(3K + 12) (seg_stride in
+        floats), QPP interleaver (f1, f2), n_iter iterations.  Outputs dense per block: bits [K] (one per byte, or packed
+        MSB-first), a-posteriori llr [K] float32."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TurboOut(addr(d_bits), int(bits_mode), addr(d_llr_out))
+        check(self.lib.ofdm_turbo_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                                int(f1), int(f2), int(n_iter), C.byref(out), ptr(stream)))
 
     # ---- Gold-sequence descrambling in front of the decoder, CRC check behind it (TS 36.211 7.2, TS 36.212 5.1.1) ----
     def reserve_bitproc(self):
@@ -511,6 +538,13 @@ class TxEngine:
         TS 36.212 5.1.4.2: E coded bits per block from bit 0 of the segment, then zeros."""
         check(self.lib.ofdm_tx_tbcc_encode_rm_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
                                                      int(E), ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
+
+    def turbo_encode_frames(self, d_info, n_seg, blocks_per_seg, K, f1, f2, d_coded, seg_bits, info_mode=BITS_UNPACKED,
+                            coded_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_turbo_encode_frames: d_info dense [n_seg][blocks_per_seg][K] bits -> d_coded [n_seg][seg_bits]: 3K + 12 coded
+        bits per block (QPP interleaver f1, f2; 12 tail bits) from bit 0 of the segment, then zeros."""
+        check(self.lib.ofdm_tx_turbo_encode_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
+                                                   int(f1), int(f2), ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
 
     # ---- CRC attach in front of the encoder, Gold-sequence scrambling behind it (TS 36.212 5.1.1, TS 36.211 7.2) ----
     def reserve_bitproc(self):
