@@ -463,8 +463,8 @@ int ofdm_rx_reserve_bitproc(ofdm_rx* h);
 /* ------------------------------------------------------------------------------------------ channel code (LTE turbo)
  * The rate-1/3 turbo code of TS 36.212 5.1.3.2 -- two 8-state constituent encoders around a QPP interleaver, with trellis
  * termination -- on the frame-batched path: the data channel's code next to the TBCC above, with an iterative max-log-MAP
- * decoder.  An extension like the TBCC: the reference has no channel code, so this text is the contract.  Rate matching
- * (5.1.4.1), code-block segmentation and the table of 3GPP (f1, f2) pairs are not part of it.
+ * decoder.  An extension like the TBCC: the reference has no channel code, so this text is the contract.  Code-block
+ * segmentation and the table of 3GPP (f1, f2) pairs are not part of it; rate matching (5.1.4.1) is the block behind this one.
  * Code block: K information bits c[0..K), K a multiple of 8 with 40 <= K <= 6144 (LTE's 188 sizes are a subset).
  * Interleaver: pi(i) = (f1 i + f2 i^2) mod K with 0 <= f1, f2 < K, handed over by the caller.  A call whose (K, f1, f2) is not a
  *   permutation of 0 .. K-1 returns OFDM_ERR_INVALID before anything is enqueued (O(K) host work per call).
@@ -526,6 +526,65 @@ int ofdm_rx_reserve_turbo(ofdm_rx* h, int64_t n_blocks, int32_t K);
  * count, a batch beyond the kernel's index range) return OFDM_ERR_INVALID before anything is enqueued. */
 int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
                              int32_t f1, int32_t f2, int32_t n_iter, const ofdm_turbo_out* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------ rate matching (LTE turbo)
+ * The three sub-block interleavers, the circular buffer with its limit Ncb and the redundancy versions of TS 36.212 5.1.4.1
+ * around the code above: E rate-matched bits per block in place of the 3K + 12 of e[3i+j], on the transmit side as an encoder
+ * of its own and on the receive side as a de-matching stage that can add a retransmission into an existing soft buffer (HARQ
+ * chase or incremental-redundancy combining).  An extension like the code itself: this text is the contract.
+ * Geometry: K, f1, f2 as above; D = K + 4; the three streams dj[i], i < D, are exactly the coded order e[3i + j] above (the 12
+ *   tail values already sit there as d0 .. d2 of i = K .. K+3).  R = ceil(D / 32), Kpi = 32R, ND = Kpi - D (K is a multiple of 8,
+ *   so ND is 4, 12, 20 or 28), Kw = 3 Kpi.
+ * Sub-block interleaver: P[c] is the 5-bit reversal of c, <0,16,8,24,4,20,12,28,2,18,10,26,6,22,14,30,1,17,..,31> (not the
+ *   TBCC's P).  d0 and d1: the stream, prefixed with ND NULLs, is written row by row into an R x 32 matrix; column c of the
+ *   permuted matrix is column P[c] of it; read column by column it is v0 resp. v1.  d2: with y = ND NULLs followed by d2,
+ *   v2[k] = y[pi2(k)], pi2(k) = (P[floor(k / R)] + 32 (k mod R) + 1) mod Kpi.
+ * Circular buffer: w[k] = v0[k], w[Kpi + 2k] = v1[k], w[Kpi + 2k + 1] = v2[k], k < Kpi.
+ * Selection: buffer length Ncb with Kpi <= Ncb <= Kw (an argument of 0 means Kw), redundancy version rv in 0 .. 3,
+ *   k0 = R (2 ceil(Ncb / (8R)) rv + 2); e_k, k < E, are the entries of w[(k0 + j) mod Ncb], j = 0, 1, 2, .., that are not NULL,
+ *   in order.  Navail = the entries of w[0 .. Ncb) that are not NULL (3K + 12 at Ncb = Kw); 1 <= E <= 16 Navail, so that a coded
+ *   bit is sent at most 16 times.
+ * rv per call or per segment: the scalar rv, or with d_rv != NULL one int32 per segment on the device of which the low two bits
+ *   are read (the scalar is then not used; a batch holds transport blocks at different HARQ rounds).
+ * Closed form: the NULLs of v0 and v1 are row 0 of the columns with P[c] < ND, those of v2 row 0 of the columns with
+ *   P[c] < ND - 1 and its last entry (pi2 = 0).  d0[i] and d1[i] sit at column P[y & 31], row y >> 5 of their stream with
+ *   y = ND + i, d2[i] at the same place for y - 1.  The rank of a place -- the entries in front of it that are not NULL -- is a
+ *   popcount over the 32-bit mask of those columns plus the interlacing; the first transmission of a coded bit is
+ *   n0 = (rank - rank(k0)) mod Navail and its copies follow every Navail bits.
+ * Segments: the TBCC rate-matching rules with E -- block b has its bits at segment bit b*E and its LLRs at
+ *   d_llr + s*seg_stride + b*E; blocks_per_seg*E <= seg_bits (encoder), seg_stride >= blocks_per_seg*E (receive side); filler
+ *   zeros follow the last block.  E need not be a multiple of 8: packed blocks may start inside a byte.
+ * De-matching, IEEE float32 in this order: v(x) = x if x is finite, else 0.  For coded bit dj[i] with n0 the index of its
+ *   first transmission in e: it has none if its place in w is >= Ncb or if n0 >= E, and then L = +0; otherwise L = v(l[n0]) and
+ *   then L = L + v(l[n0 + m Navail]) for m = 1, 2, .. while the index is < E, in increasing m.  accumulate == 0:
+ *   out[3i + j] = L, stored as summed (an overflowed sum as +-inf, a single -0 as -0).  accumulate != 0: out[3i + j] = old + L
+ *   with old the float already there, read as is: one float32 addition after L is complete.  The first transmission of a block
+ *   uses accumulate == 0 or a zeroed buffer.  The output is what ofdm_turbo_decode_frames reads, 3K + 12 floats per block; that
+ *   decoder counts inputs that are not finite as 0.  The de-matched buffer IS the HARQ soft buffer, so there is no decoder
+ *   variant that de-matches while it loads.
+ * Deterministic: a block's outputs depend on its own E LLRs only, plus its old soft values when accumulating (no atomics). */
+/* floor(seg_bits / E): the blocks a segment can carry.  Host arithmetic; OFDM_ERR_INVALID for a bad K, E outside
+ * 1 .. 16 (3K + 12) or seg_bits < 0. */
+int64_t ofdm_turbo_rm_blocks(int64_t seg_bits, int32_t K, int32_t E);
+/* *k0 and *n_avail (either may be NULL) of (K, Ncb, rv).  Host arithmetic through the kernels' own geometry routine; no device. */
+int ofdm_turbo_rm_info(int32_t K, int32_t Ncb, int32_t rv, int32_t* k0, int32_t* n_avail);
+/* ofdm_tx_turbo_encode_frames with E rate-matched bits per block: the same layouts, filler, no-op and error rules
+ * (seg_bits >= blocks_per_seg*E), and OFDM_ERR_INVALID for E or Ncb out of range or a scalar rv outside 0 .. 3 while it is in
+ * use.  One launch, no allocation. */
+int ofdm_tx_turbo_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                   int32_t K, int32_t f1, int32_t f2, int32_t E, int32_t Ncb, int32_t rv, const int32_t* d_rv,
+                                   uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream);
+/* d_out[s*out_stride + b*(3K+12) + 3i + j] = L of dj[i], or old + L (out_stride in floats, >= blocks_per_seg*(3K+12)).
+ * Asynchronous on `stream` (NULL = the handle's stream), one launch, no allocation, no host synchronisation; n_seg == 0 or
+ * blocks_per_seg == 0 is a no-op.  OFDM_ERR_INVALID before anything is enqueued for a NULL handle, a bad K, E or Ncb out of
+ * range, a scalar rv outside 0 .. 3 while in use, a stride that is too short, a negative count or a batch beyond the index
+ * range. */
+int ofdm_turbo_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                                   int32_t K, int32_t E, int32_t Ncb, int32_t rv, const int32_t* d_rv, int32_t accumulate,
+                                   float* d_out, int64_t out_stride, void* stream);
+/* Load the kernels of this block on the handle's device: call before capturing one of its calls into a hipGraph. */
+int ofdm_tx_reserve_turbo_rm(ofdm_tx* h);
+int ofdm_rx_reserve_turbo_rm(ofdm_rx* h);
 
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the

@@ -1,5 +1,7 @@
 // capi_turbo.hip -- the LTE turbo code on the frame-batched path (definition: include/ofdm_mi355x.h): the
 // host-only block count and interleaver check, the encode call of the transmitter handle, reserve and decode of the receiver handle.
+// Behind them the same for its rate matching: block count and geometry on the host, the rate-matching encoder,
+// the de-matching call and the two reserve calls.
 #include "capi_internal.hpp"
 
 namespace {
@@ -12,6 +14,15 @@ const char* turbo_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K,
         return "batch beyond the kernels' index range";
     if (f1 < 0 || f1 >= K || f2 < 0 || f2 >= K) return "f1 and f2 must lie in 0 .. K-1";
     if (!turbo_qpp_valid(K, f1, f2)) return "(f1 i + f2 i^2) mod K is not a permutation of 0 .. K-1";
+    return "";
+}
+// the rate-matching geometry on top of K: Ncb (0 = Kw) and E against the buffer's non-NULL entries; "" = fine
+constexpr const char* TURBO_RM_BAD_NCB = "Ncb must be 0 or lie in Kpi .. 3 Kpi, Kpi = 32 ceil((K + 4) / 32)";
+bool turbo_rm_ncb_ok(int32_t K, int64_t Ncb) { return Ncb == 0 || (Ncb >= turbo_rm_kpi(K) && Ncb <= 3 * turbo_rm_kpi(K)); }
+const char* turbo_rm_bad_geometry(int32_t K, int64_t E, int64_t Ncb, int32_t rv, const int32_t* d_rv) {
+    if (!turbo_rm_ncb_ok(K, Ncb)) return TURBO_RM_BAD_NCB;
+    if (E < 1 || E > int64_t(TURBO_RM_MAX_COPIES) * turbo_rm_geom(K, 1, int(Ncb)).navail) return "E must lie in 1 .. 16 Navail";
+    if (!d_rv && (rv < 0 || rv > 3)) return "rv must lie in 0 .. 3";
     return "";
 }
 bool turbo_wanted(const ofdm_turbo_out* o) { return o && (o->bits || o->llr); }
@@ -114,6 +125,105 @@ int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int6
     a.llr_out = out->llr;
     a.q = turbo_qpp(K, f1, f2);
     HIP_TRY(launch_turbo_decode(a, s));
+    return OFDM_OK;
+}
+
+// ---- rate matching (TS 36.212 5.1.4.1)
+int64_t ofdm_turbo_rm_blocks(int64_t seg_bits, int32_t K, int32_t E) {
+    if (!turbo_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rm_blocks: %s", TURBO_BAD_K);
+    if (E < 1 || E > TURBO_RM_MAX_COPIES * (3 * int64_t(K) + 12)) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rm_blocks: E must lie in 1 .. 16 (3K + 12)");
+    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rm_blocks: negative seg_bits");
+    return seg_bits / E;
+}
+
+int ofdm_turbo_rm_info(int32_t K, int32_t Ncb, int32_t rv, int32_t* k0, int32_t* n_avail) {
+    if (!turbo_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rm_info: %s", TURBO_BAD_K);
+    const char* bad = turbo_rm_bad_geometry(K, 1, Ncb, rv, nullptr);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rm_info: %s", bad);
+    const TurboRmGeom g = turbo_rm_geom(K, 1, Ncb);
+    if (k0) *k0 = turbo_rm_k0(K, g.Ncb, rv);
+    if (n_avail) *n_avail = g.navail;
+    return OFDM_OK;
+}
+
+int ofdm_tx_reserve_turbo_rm(ofdm_tx* h) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_turbo_rm: null handle");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(turbo_rm_prepare());
+    return OFDM_OK;
+}
+
+int ofdm_rx_reserve_turbo_rm(ofdm_rx* h) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo_rm: null handle");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(turbo_rm_prepare());
+    return OFDM_OK;
+}
+
+int ofdm_tx_turbo_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
+                                   int32_t K, int32_t f1, int32_t f2, int32_t E, int32_t Ncb, int32_t rv, const int32_t* d_rv,
+                                   uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: null handle");
+    const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
+    if (!*bad) bad = turbo_rm_bad_geometry(K, E, Ncb, rv, d_rv);
+    if (!*bad) {
+        if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * E) bad = "seg_bits < blocks_per_seg * E";
+        else if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) bad = "packed coded bits need seg_bits % 8 == 0";
+        else if (!tbcc_items_ok(n_seg, seg_bits)) bad = "batch beyond the kernel's index range";
+    }
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: %s", bad);
+    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
+    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: null buffer");
+    TurboEncRmArgs a{};
+    a.info = d_info;
+    a.info_mode = info_mode;
+    a.n_seg = n_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.coded = d_coded;
+    a.coded_mode = coded_mode;
+    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    a.q = turbo_qpp(K, f1, f2);
+    a.g = turbo_rm_geom(K, E, Ncb);
+    a.rv = rv;
+    a.rv_dev = d_rv;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_turbo_encode_rm(a, pick_stream(h, stream)));
+    return OFDM_OK;
+}
+
+int ofdm_turbo_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                                   int32_t K, int32_t E, int32_t Ncb, int32_t rv, const int32_t* d_rv, int32_t accumulate,
+                                   float* d_out, int64_t out_stride, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rate_dematch_frames: null handle");
+    const int64_t per = 3 * int64_t(K) + 12;
+    const char* bad = "";
+    if (!turbo_valid_k(K)) bad = TURBO_BAD_K;
+    else if (n_seg < 0 || blocks_per_seg < 0) bad = "negative count";
+    else if (*(bad = turbo_rm_bad_geometry(K, E, Ncb, rv, d_rv))) {}
+    else if (seg_stride < int64_t(blocks_per_seg) * E) bad = "seg_stride < blocks_per_seg * E";
+    else if (out_stride < int64_t(blocks_per_seg) * per) bad = "out_stride < blocks_per_seg * (3K + 12)";
+    // one thread per output LLR in workgroups of 256: the grid's x range bounds n_seg * blocks_per_seg * (3K + 12)
+    else if (!tbcc_items_ok(n_seg, seg_stride) || !tbcc_items_ok(n_seg, out_stride) || n_seg > TBCC_MAX_BLOCKS ||
+             (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS * int64_t(256) / per / blocks_per_seg))
+        bad = "batch beyond the kernel's index range";
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rate_dematch_frames: %s", bad);
+    if (n_seg == 0 || blocks_per_seg == 0) return OFDM_OK;
+    if (!d_llr || !d_out) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rate_dematch_frames: null buffer");
+    TurboDematchArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_seg * blocks_per_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.K = K;
+    a.out = d_out;
+    a.out_stride = out_stride;
+    a.accumulate = accumulate;
+    a.g = turbo_rm_geom(K, E, Ncb);
+    a.rv = rv;
+    a.rv_dev = d_rv;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(launch_turbo_dematch(a, pick_stream(h, stream)));
     return OFDM_OK;
 }
 

@@ -342,6 +342,54 @@ hipError_t launch_turbo_encode(const TurboEncArgs& a, hipStream_t s);
 hipError_t launch_turbo_decode(const TurboDecArgs& a, hipStream_t s);
 hipError_t turbo_decode_prepare();       // loads the decoder's code object (before a stream capture)
 
+// ---- turbo rate matching (turbo_rm.hip; TS 36.212 5.1.4.1; contract: include/ofdm_mi355x.h)
+constexpr int TURBO_RM_MAX_COPIES = 16;  // E <= 16 Navail
+struct TurboRmGeom {         // what the closed form of the sub-block interleavers and the circular buffer needs, all of it from K, E, Ncb
+    int E;                   // rate-matched bits per block
+    int D, R, ND, Kpi;       // K + 4, rows of the 32-column matrices = ceil(D / 32), NULLs in front of a stream = 32R - D, 32R
+    int Ncb, navail;         // buffer length (Kpi .. 3 Kpi) and the non-NULL entries of w[0 .. Ncb)
+    int rank0[4];            // per rv: the non-NULL entries of w[0 .. k0)
+    uint32_t mask01, mask2;  // bit c set iff column c of v0 / v1 (P[c] < ND) resp. of v2 (P[c] < ND - 1) starts with a NULL
+};
+// non-NULL entries in front of (column c, row r) of a stream whose NULLs are row 0 of mask's columns; c < 32
+__host__ __device__ inline int turbo_rm_stream_count(uint32_t mask, int R, int c, int r) {
+    return c * R + r - __builtin_popcount(mask & ((1u << c) - 1u)) - (r > 0 ? int((mask >> c) & 1u) : 0);
+}
+// non-NULL entries of w[0 .. p), 0 <= p <= 3 Kpi: v0, then v1 and v2 interlaced; v2's last entry is its extra NULL
+__host__ __device__ inline int turbo_rm_count(const TurboRmGeom& g, int p) {
+    auto stream = [&](uint32_t mask, int k) { return k >= g.Kpi ? g.D : turbo_rm_stream_count(mask, g.R, k / g.R, k % g.R); };
+    if (p <= g.Kpi) return stream(g.mask01, p);
+    const int q = p - g.Kpi;
+    return g.D + stream(g.mask01, (q + 1) >> 1) + stream(g.mask2, q >> 1);
+}
+inline int turbo_rm_kpi(int K) { return 32 * ((K + 4 + 31) / 32); }
+inline int turbo_rm_k0(int K, int Ncb, int rv) {             // Ncb already resolved (not 0)
+    const int R = turbo_rm_kpi(K) / 32;
+    return R * (2 * ((Ncb + 8 * R - 1) / (8 * R)) * rv + 2);
+}
+TurboRmGeom turbo_rm_geom(int K, int E, int Ncb);            // Ncb = 0 means 3 Kpi; E is only stored
+struct TurboEncRmArgs : TurboEncArgs {   // coded: blocks_per_seg*E bits from bit 0, then zeros
+    TurboRmGeom g;
+    int rv;                  // redundancy version of every segment, unless
+    const int32_t* rv_dev;   // [n_seg] on the device (low two bits), or null
+};
+struct TurboDematchArgs {
+    const float* llr;        // block (seg, b) = E floats at llr + seg*seg_stride + b*E
+    int64_t seg_stride;      // floats
+    int64_t n_blocks;        // n_seg * blocks_per_seg
+    int blocks_per_seg, K;
+    float* out;              // block (seg, b) = 3K+12 floats at out + seg*out_stride + b*(3K+12), [3i + j]: what TurboDecArgs::llr takes
+    int64_t out_stride;      // floats
+    int accumulate;          // != 0: out = old + L
+    TurboRmGeom g;
+    int rv;
+    const int32_t* rv_dev;
+};
+int turbo_rm_group(int E, int coded_mode);                   // blocks per workgroup of the encoder: their bits end on a byte
+hipError_t launch_turbo_encode_rm(const TurboEncRmArgs& a, hipStream_t s);
+hipError_t launch_turbo_dematch(const TurboDematchArgs& a, hipStream_t s);
+hipError_t turbo_rm_prepare();           // loads both kernels (before a stream capture)
+
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
 // batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs

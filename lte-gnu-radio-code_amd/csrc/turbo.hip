@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "ofdm_launch.hpp"
+#include "turbo_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -19,43 +20,7 @@ namespace ofdm {
 
 namespace {
 
-// pi(i) = (f1 i + f2 i^2) mod K in 32-bit arithmetic: every product stays below 2^26 for K <= 6144
-__device__ __forceinline__ unsigned turbo_qpp_at(const TurboQpp& q, unsigned i) {
-    const unsigned K = unsigned(q.K);
-    return ((unsigned(q.f1) * i) % K + ((i * i) % K) * unsigned(q.f2) % K) % K;
-}
-__device__ __forceinline__ unsigned turbo_mod_add(unsigned a, unsigned b, unsigned K) {
-    const unsigned s = a + b;                                // a, b < K
-    return s >= K ? s - K : s;
-}
-
 // ------------------------------------------------------------------------------------------ encoder
-__device__ __forceinline__ unsigned turbo_info_bit(const uint8_t* blk, int packed, unsigned i) {
-    return packed ? (unsigned(blk[i >> 3]) >> (7 - (i & 7))) & 1u : unsigned(blk[i]) & 1u;
-}
-// one step of a constituent encoder: state s = 4 r1 + 2 r2 + r3, input u -> parity z, next state
-__device__ __forceinline__ unsigned turbo_rsc_step(unsigned s, unsigned u, unsigned& z) {
-    const unsigned r1 = s >> 2, r2 = (s >> 1) & 1u, r3 = s & 1u;
-    const unsigned a = u ^ r2 ^ r3;
-    z = a ^ r1 ^ r3;
-    return (a << 2) | (s >> 1);
-}
-// n steps with input 0 (the register's free response; its period is 7)
-__device__ __forceinline__ unsigned turbo_rsc_free(unsigned s, int n) {
-    for (; n > 0; --n) s = ((((s >> 1) ^ s) & 1u) << 2) | (s >> 1);
-    return s;
-}
-// the three termination steps from state s: x_K z_K x_{K+1} z_{K+1} x_{K+2} z_{K+2}, the first on top (bit 5)
-__device__ __forceinline__ unsigned turbo_rsc_tail(unsigned s) {
-    unsigned bits = 0u;
-    for (int j = 0; j < 3; ++j) {
-        const unsigned r1 = s >> 2, r2 = (s >> 1) & 1u, r3 = s & 1u;
-        bits = (bits << 2) | ((r2 ^ r3) << 1) | (r1 ^ r3);
-        s >>= 1;
-    }
-    return bits;
-}
-
 // One wave per PAIR of consecutive blocks of a segment, 32 lanes per block: 2 (3K + 12) coded bits are a whole number of bytes,
 // so that a wave's packed output starts and ends on a byte of its own although a single block (3K + 12 = 4 mod 8) does not.
 //   A  every lane runs both constituent encoders over its chunk of ceil(K / 32) steps from state 0 (the zero-state response);

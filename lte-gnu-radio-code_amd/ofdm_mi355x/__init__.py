@@ -3,5 +3,5 @@ from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, COMPAT_RXOFDM, COMPAT_
                    LIB_PATH, OfdmError, OfdmLibraryError, PILOT_CPE, PILOT_CPE_SLOPE, load)
 from .engine import (DeviceBuffer, FoEngine, RxEngine, TrkEngine, TxEngine, bins_p, count_bit_errors, crc_bits,  # noqa: F401
                      crc_compute, gold_bits, tbcc_blocks, tbcc_rm_blocks, turbo_blocks, turbo_qpp_check,
-                     zadoff_chu)
+                     turbo_rm_blocks, turbo_rm_info, zadoff_chu)
 from .safe_pickle import UnsafePickleError, load_ndarray  # noqa: F401

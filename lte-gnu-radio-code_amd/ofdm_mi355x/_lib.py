@@ -176,6 +176,15 @@ PROTOTYPES = {
     "ofdm_rx_reserve_turbo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "ofdm_turbo_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.POINTER(TurboOut), C.c_void_p]),
+    "ofdm_turbo_rm_blocks": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "ofdm_turbo_rm_info": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ofdm_tx_turbo_encode_rm_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                 C.c_int64, C.c_void_p]),
+    "ofdm_turbo_rate_dematch_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ofdm_tx_reserve_turbo_rm": (C.c_int, [C.c_void_p]),
+    "ofdm_rx_reserve_turbo_rm": (C.c_int, [C.c_void_p]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

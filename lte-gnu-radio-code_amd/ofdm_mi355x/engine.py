@@ -94,6 +94,19 @@ def turbo_blocks(seg_bits: int, K: int) -> int:
     return int(check(_lib.load().ofdm_turbo_blocks(int(seg_bits), int(K))))
 
 
+def turbo_rm_blocks(seg_bits: int, K: int, E: int) -> int:
+    """ofdm_turbo_rm_blocks: the rate-matched turbo code blocks (K information bits in E coded bits) a segment of seg_bits carries."""
+    return int(check(_lib.load().ofdm_turbo_rm_blocks(int(seg_bits), int(K), int(E))))
+
+
+def turbo_rm_info(K: int, Ncb: int = 0, rv: int = 0) -> tuple:
+    """ofdm_turbo_rm_info: (k0, Navail) of the turbo rate matcher's circular buffer for block size K, buffer length Ncb (0 = all
+    of it) and redundancy version rv; host arithmetic."""
+    k0, navail = C.c_int32(), C.c_int32()
+    check(_lib.load().ofdm_turbo_rm_info(int(K), int(Ncb), int(rv), C.byref(k0), C.byref(navail)))
+    return int(k0.value), int(navail.value)
+
+
 def turbo_qpp_check(K: int, f1: int, f2: int) -> bool:
     """ofdm_turbo_qpp_check: True iff K is a valid block size, 0 <= f1, f2 < K and (f1 i + f2 i^2) mod K is a permutation."""
     return _lib.load().ofdm_turbo_qpp_check(int(K), int(f1), int(f2)) == 0
@@ -320,6 +333,19 @@ class RxEngine:
         check(self.lib.ofdm_turbo_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                 int(f1), int(f2), int(n_iter), C.byref(out), ptr(stream)))
 
+    def reserve_turbo_rm(self):
+        """Loads the turbo rate-matching kernels (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_turbo_rm(self._h))
+
+    def turbo_rate_dematch_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, E, d_out, out_stride, Ncb=0, rv=0, d_rv=None,
+                                  accumulate=False, stream=None):
+        """ofdm_turbo_rate_dematch_frames: block (s, b) = the E float32 LLRs at d_llr + s*seg_stride + b*E -> its 3K + 12
+        de-matched LLRs at d_out + s*out_stride + b*(3K + 12), what turbo_decode_frames reads; redundancy version rv (or d_rv, one
+        device int32 per segment), buffer length Ncb (0 = all of it).  accumulate adds into the floats already there (HARQ)."""
+        check(self.lib.ofdm_turbo_rate_dematch_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                                      int(E), int(Ncb), int(rv), ptr(d_rv), int(bool(accumulate)), ptr(d_out),
+                                                      int(out_stride), ptr(stream)))
+
     # ---- Gold-sequence descrambling in front of the decoder, CRC check behind it (TS 36.211 7.2, TS 36.212 5.1.1) ----
     def reserve_bitproc(self):
         """Loads the descrambling and CRC kernels (before a graph capture)."""
@@ -545,6 +571,19 @@ class TxEngine:
         bits per block (QPP interleaver f1, f2; 12 tail bits) from bit 0 of the segment, then zeros."""
         check(self.lib.ofdm_tx_turbo_encode_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
                                                    int(f1), int(f2), ptr(d_coded), int(coded_mode), int(seg_bits), ptr(stream)))
+
+    def reserve_turbo_rm(self):
+        """Loads the turbo rate-matching kernels (before a graph capture)."""
+        check(self.lib.ofdm_tx_reserve_turbo_rm(self._h))
+
+    def turbo_encode_rm_frames(self, d_info, n_seg, blocks_per_seg, K, f1, f2, E, d_coded, seg_bits, Ncb=0, rv=0, d_rv=None,
+                               info_mode=BITS_UNPACKED, coded_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_turbo_encode_rm_frames: turbo_encode_frames with the sub-block interleavers and circular-buffer rate matching of
+        TS 36.212 5.1.4.1: E coded bits per block from redundancy version rv (or d_rv, one device int32 per segment) of a buffer
+        of Ncb entries (0 = all of it)."""
+        check(self.lib.ofdm_tx_turbo_encode_rm_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
+                                                      int(f1), int(f2), int(E), int(Ncb), int(rv), ptr(d_rv), ptr(d_coded),
+                                                      int(coded_mode), int(seg_bits), ptr(stream)))
 
     # ---- CRC attach in front of the encoder, Gold-sequence scrambling behind it (TS 36.212 5.1.1, TS 36.211 7.2) ----
     def reserve_bitproc(self):
