@@ -586,6 +586,87 @@ int ofdm_turbo_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg
 int ofdm_tx_reserve_turbo_rm(ofdm_tx* h);
 int ofdm_rx_reserve_turbo_rm(ofdm_rx* h);
 
+/* ------------------------------------------------------------------------------------------ transport block (LTE turbo)
+ * The layer that makes the three blocks above usable on a real payload: transport-block CRC (TS 36.212 5.1.1), code-block
+ * segmentation with a CRC per code block (5.1.2), the two rate-matching sizes of a transport block (5.1.4.1.2) and code-block
+ * concatenation (5.1.5), around the encode / de-match / decode calls above, which it uses as they are.  An extension like the
+ * code itself: this text is the contract.
+ * Valid K here: LTE's 188 sizes -- 40 .. 512 in steps of 8, 528 .. 1024 in steps of 16, 1056 .. 2048 in steps of 32,
+ *   2112 .. 6144 in steps of 64.
+ * Segmentation of a transport block of A bits, A a multiple of 8 with 8 <= A <= 2^20 - 24, at the maximum code block size Z, one
+ *   of the valid K (an argument of 0 means 6144; smaller values exist so that every branch can be reached with small blocks):
+ *   B = A + 24: the payload, then its CRC24A with a zero mask, in the arithmetic of the CRC block above (p0 first).
+ *   B <= Z: L = 0, C = 1, B' = B.  Otherwise L = 24, C = ceil(B / (Z - 24)), B' = B + 24 C.
+ *   K+ = the smallest valid K with C K >= B'.  C = 1: C+ = 1, C- = 0, K- = 0.  Otherwise K- = the largest valid K below K+,
+ *   dK = K+ - K-, C- = floor((C K+ - B') / dK), C+ = C - C-; at K+ = 40, where there is no K-, dK = 8 and K- = 0, and a case with
+ *   C- > 0 there is OFDM_ERR_INVALID.  F = C+ K+ + C- K- - B'.
+ *   Blocks r < C- have K- bits, the others K+.  Block 0 starts with F zeros; then each block carries its K_r - L bits of the
+ *   B-bit sequence in order, and with L = 24 the CRC24B (zero mask) of its first K_r - 24 bits, the filler zeros included,
+ *   follows.  A, B', F and every K are multiples of 8, so every packed block and every slice is byte aligned.
+ * Filler bits -- a DEVIATION from TS 36.212: they are encoded and rate-matched as ordinary zeros and not marked <NULL> as
+ *   5.1.3.2.1 and 5.1.4.1.1 ask, on the transmit and on the receive side alike, so the two sides of this library agree with
+ *   each other and, for F > 0, with nobody else.  F is reported: a host that needs conformance refuses F > 0.  The transport
+ *   block sizes of TS 36.213 are believed to give F = 0 throughout; that is a belief, it has not been checked here.
+ * Rate matching: G coded bits per transport block in units of q = N_L Q_m >= 1, G % q == 0.  G' = G / q, gamma = G' mod C;
+ *   E_r = q floor(G' / C) (E0) for r <= C - gamma - 1, else q ceil(G' / C) (E1).  Every E_r has to lie in 1 .. 16 Navail of its
+ *   block.  Soft-buffer limit N_IR (0 = none): Ncb_r = min(floor(N_IR / C), Kw_r), OFDM_ERR_INVALID if that is below Kpi_r.
+ * Groups: the boundaries C- and C - gamma cut 0 .. C into at most three contiguous runs of blocks with one (K, E) each, in block
+ *   order; ofdm_tb_geom names them.  Workspaces and the soft buffer are laid out by them.
+ * Interleavers: the caller supplies one (f1, f2) for K- and one for K+ (the table of 3GPP pairs is not part of this library);
+ *   each one that has blocks is held to the rule of ofdm_turbo_qpp_check, the other is not looked at.
+ * Codeword: the blocks' E_r bits back to back, r = 0 .. C-1, G bits; transport block t at bit t*cw_bits of the buffer
+ *   (cw_bits >= G, zeros from G on; packed codewords need cw_bits % 8 == 0).  On the receive side its LLRs at
+ *   d_llr + t*llr_stride (floats, llr_stride >= G).
+ * HARQ soft buffer: per transport block sum_r (3 K_r + 12) floats in block order -- what the de-matcher writes and the decoder
+ *   reads -- at d_soft + t*soft_stride (soft_stride >= that sum).  It belongs to the caller and goes in and out; `accumulate`
+ *   has the de-matcher's meaning, and rv / d_rv (one value per transport block) the rate matcher's.
+ * Results: the A payload bits, tb_ok = (CRC24A of the re-joined first A bits == the 24 bits behind them), that difference as
+ *   `syndrome`, and cb_ok[t][r] = the same for block r's CRC24B (1 with L = 0).  Deterministic, no atomics. */
+typedef struct ofdm_tb_geom {
+    int32_t A, Z, B, L, C, K_plus, K_minus, C_plus, C_minus, F, n_groups;
+    int32_t G, q, gamma, E0, E1, Ncb_minus, Ncb_plus;   /* Ncb resolved (Kw without a limit), 0 for a K without blocks; all 0 at G == 0 */
+    struct { int32_t first, count, K, E; int64_t cw_bit_offset, soft_offset; } group[3];
+    int64_t soft_floats;       /* sum_r (3 K_r + 12)                                                                 */
+} ofdm_tb_geom;
+/* The smallest valid K >= bits (40 for every bits <= 40), or OFDM_ERR_INVALID above 6144.  Host arithmetic. */
+int32_t ofdm_turbo_k_next(int32_t bits);
+/* Everything above for one transport block.  G == 0: the segmentation alone (q and N_IR are not looked at; the groups are the
+ * runs of one K, with E = 0 and cw_bit_offset = 0).  Host arithmetic; OFDM_ERR_INVALID for anything out of range. */
+int ofdm_tb_geometry(int32_t A, int32_t Z, int64_t G, int32_t q, int64_t N_IR, ofdm_tb_geom* out);
+/* ofdm_crc_compute without its length limit: n_bits a multiple of 8 with 8 <= n_bits <= 2^30.  Host arithmetic through the
+ * kernels' own chunk-and-combine routine (256 runs, each multiplied by x^(bits behind it) mod g, XORed); no device. */
+int ofdm_crc_compute_long(int32_t kind, const uint8_t* host_bits_packed, int64_t n_bits, uint32_t* crc);
+/* d_payload dense [n_tb][A] (or [A/8]) -> d_cw [n_tb][cw_bits] (or [cw_bits/8]).  Asynchronous on `stream` (NULL = the handle's
+ * stream): the segment kernel, one rate-matching encoder launch per group, the concatenation kernel; no host synchronisation
+ * and, once reserved, no allocation.  The workspace belongs to the handle: calls on one handle must not overlap on the device.
+ * n_tb == 0 is a no-op.  Argument errors (NULL handle, anything ofdm_tb_geometry refuses, G == 0, a pair that is no permutation,
+ * bad modes, a scalar rv outside 0 .. 3 while in use, cw_bits < G, a batch beyond the kernels' index range) return
+ * OFDM_ERR_INVALID before anything is enqueued, and so does, inside a capture, a call that would have to grow the workspace. */
+int ofdm_tx_tb_encode_frames(ofdm_tx* h, const uint8_t* d_payload, int32_t payload_mode, int64_t n_tb, int32_t A, int32_t Z,
+                             int64_t G, int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus,
+                             int32_t f2_plus, int32_t rv, const int32_t* d_rv, uint8_t* d_cw, int32_t cw_mode, int64_t cw_bits,
+                             void* stream);
+typedef struct ofdm_tb_out {     /* DEVICE pointers; NULL = not wanted */
+    uint8_t*  payload;       /* dense [n_tb][A] or [n_tb][A/8]                                                  */
+    int32_t   payload_mode;  /* ofdm_bits_mode of payload                                                       */
+    uint8_t*  tb_ok;         /* [n_tb]                                                                          */
+    uint8_t*  cb_ok;         /* [n_tb][C]                                                                       */
+    uint32_t* syndrome;      /* [n_tb] CRC24A of the re-joined payload ^ the received parity                    */
+} ofdm_tb_out;
+/* One de-matching launch per group straight out of d_llr into d_soft, one decoder launch per K on d_soft in place, the
+ * desegment kernel.  The rules of the encode call; additionally n_iter in 1 .. 16, llr_stride >= G, soft_stride >= soft_floats,
+ * and `out` == NULL is an argument error (an `out` without any pointer de-matches and stops there: the soft buffer is an
+ * output of its own).  The decoder's workspace is the one of ofdm_rx_reserve_turbo. */
+int ofdm_tb_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t llr_stride, int32_t A, int32_t Z, int64_t G,
+                          int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus, int32_t f2_plus,
+                          int32_t rv, const int32_t* d_rv, int32_t n_iter, int32_t accumulate, float* d_soft, int64_t soft_stride,
+                          const ofdm_tb_out* out, void* stream);
+/* Size the handle's workspace for n_tb transport blocks of this geometry per call (transmit: the packed code blocks and G bytes
+ * of encoder output per transport block; receive: the packed decoded blocks, and the turbo decoder's workspace for both K) and
+ * load the kernels; the workspaces only grow.  Growing waits for the device, so call these before capturing into a hipGraph. */
+int ofdm_tx_reserve_tb(ofdm_tx* h, int64_t n_tb, int32_t A, int32_t Z, int64_t G, int32_t q);
+int ofdm_rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z);
+
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the
  * gr-RXOFDM receiver (root-37 ZC, stride cp-1, gate 0.4, linear SNR) plus a brute-force carrier

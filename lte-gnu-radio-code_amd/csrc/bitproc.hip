@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include "crc_device.hpp"
 #include "ofdm_launch.hpp"
 
 namespace ofdm {
@@ -102,9 +103,6 @@ __host__ __device__ __forceinline__ void gold_jump(const GoldTables& t, uint32_t
 // bits; a vector's four sequence bits are one nibble of an LDS word that eight neighbouring lanes share (a broadcast read).
 enum : int { GOLD_MODE_LLR = 0, GOLD_MODE_BYTES = 1, GOLD_MODE_PACKED = 2 };
 
-__device__ __forceinline__ uint32_t gold_spread4(uint32_t nib) {         // bit y -> byte y
-    return (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
-}
 // 32 sequence bits as four packed bytes in memory order (the first bit is the MSB of the first byte)
 __device__ __forceinline__ uint32_t gold_packed_word(uint32_t w) { return __builtin_bswap32(__brev(w)); }
 
@@ -184,44 +182,7 @@ __global__ void __launch_bounds__(64) gold_apply_kernel(GoldArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ CRC
-__host__ __device__ constexpr uint32_t crc_poly(int kind) { return kind == 0 ? 0x1864CFBu : kind == 1 ? 0x1800063u : kind == 2 ? 0x11021u : 0x19Bu; }
-__host__ __device__ constexpr int crc_len(int kind) { return kind <= 1 ? 24 : kind == 2 ? 16 : 8; }
-
-// remainder of v * D^L, v one byte: the entry of the byte-wise table
-__host__ __device__ constexpr uint32_t crc_table_entry(uint32_t poly, int L, uint32_t v) {
-    uint32_t reg = v << (L - 8);
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t top = (reg >> (L - 1)) & 1u;
-        reg = (reg << 1) ^ (top ? poly : 0u);
-    }
-    return reg & ((1u << L) - 1u);
-}
-// one byte further: reg' = (reg << 8 mod D^L) ^ table[crc_index(reg, byte)]
-__host__ __device__ __forceinline__ uint32_t crc_byte(uint32_t reg, uint32_t entry, int L) { return ((reg << 8) & ((1u << L) - 1u)) ^ entry; }
-__host__ __device__ __forceinline__ uint32_t crc_index(uint32_t reg, uint32_t byte, int L) { return ((reg >> (L - 8)) ^ byte) & 0xffu; }
-
-// byte i of a block (8 bits, the first one on top) in either layout; `wide`: the block starts on a word boundary
-__device__ __forceinline__ uint32_t crc_load_byte(const uint8_t* blk, bool packed, bool wide, int i) {
-    if (packed) return blk[i];
-    if (wide) {
-        const uint2 w = reinterpret_cast<const uint2*>(blk)[i];
-        return ((((w.x & 0x01010101u) * 0x08040201u) >> 20) & 0xf0u) | ((((w.y & 0x01010101u) * 0x08040201u) >> 24) & 0x0fu);
-    }
-    uint32_t v = 0u;
-#pragma unroll
-    for (int x = 0; x < 8; ++x) v |= (uint32_t(blk[8 * i + x]) & 1u) << (7 - x);
-    return v;
-}
-__device__ __forceinline__ void crc_store_byte(uint8_t* blk, bool packed, bool wide, int i, uint32_t v) {
-    if (packed) {
-        blk[i] = uint8_t(v);
-    } else if (wide) {
-        reinterpret_cast<uint2*>(blk)[i] = make_uint2(gold_spread4(__brev(v >> 4) >> 28), gold_spread4(__brev(v & 0xfu) >> 28));
-    } else {
-#pragma unroll
-        for (int x = 0; x < 8; ++x) blk[8 * i + x] = uint8_t((v >> (7 - x)) & 1u);
-    }
-}
+// generators, table step and the byte load / store of both layouts: crc_device.hpp (shared with tb.hip and the host calls)
 
 // One lane per block: the remainder of the first A bits through the byte-wise table of the call's generator, which the
 // workgroup builds in LDS (256 threads, one entry each).  ATTACH: copies the payload into the block (either layout to either

@@ -97,6 +97,9 @@ struct ofdm_rx {
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints
     float* t_ws = nullptr;
     int64_t cap_turbo = 0;               // floats
+    // ---- transport-block layer (ofdm_rx_reserve_tb): the decoder's packed bits, dense [n_tb][count][K / 8] per K
+    uint8_t* tb_ws = nullptr;
+    int64_t cap_tb = 0;                  // bytes
     int max_trials = 0;
     int scan_block = 0;                  // > 0: the batch path's sync search is screened in blocks of this many trials
     cf* d_scan_g = nullptr;              // [N + 2] recurrence kernel G, then {max |G|, 0}
@@ -183,6 +186,9 @@ struct ofdm_tx {
     int* d_pilots = nullptr;             // ascending list indices into binsP(Kd + n_pilots)
     int n_pilots = 0;
     cf pilot_value = cf{1.f, 0.f};
+    // ---- transport-block layer (ofdm_tx_reserve_tb): the packed code blocks per group, then the groups' encoder outputs
+    uint8_t* tb_ws = nullptr;
+    int64_t cap_tb = 0;                  // bytes
 };
 
 namespace {

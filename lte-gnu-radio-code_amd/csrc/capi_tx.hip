@@ -34,7 +34,7 @@ int ofdm_tx_destroy(ofdm_tx* h) {
     if (!h) return OFDM_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_dev(&h->d_tw, &h->d_zc, &h->d_sync_time, &h->d_pilots);
+    free_dev(&h->d_tw, &h->d_zc, &h->d_sync_time, &h->d_pilots, &h->tb_ws);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return OFDM_OK;

@@ -390,6 +390,54 @@ hipError_t launch_turbo_encode_rm(const TurboEncRmArgs& a, hipStream_t s);
 hipError_t launch_turbo_dematch(const TurboDematchArgs& a, hipStream_t s);
 hipError_t turbo_rm_prepare();           // loads both kernels (before a stream capture)
 
+// ---- transport-block layer (tb.hip; TS 36.212 5.1.1, 5.1.2, 5.1.5; contract: include/ofdm_mi355x.h)
+constexpr int TB_A_MIN = 8, TB_A_MAX = (1 << 20) - 24;
+constexpr int TB_THREADS = 256;          // one workgroup per transport block: the runs of its CRC24A, four waves for the code blocks
+// LTE's 188 block sizes: the smallest one >= bits and the largest one below K; 0 where there is none
+inline int turbo_k_next(int64_t bits) {
+    if (bits <= 40) return 40;
+    if (bits > TURBO_K_MAX) return 0;
+    const int64_t step = bits <= 512 ? 8 : bits <= 1024 ? 16 : bits <= 2048 ? 32 : 64;
+    return int((bits + step - 1) / step * step);
+}
+inline int turbo_k_prev(int K) { return K <= 40 ? 0 : K <= 512 ? K - 8 : K <= 1024 ? K - 16 : K <= 2048 ? K - 32 : K - 64; }
+inline bool turbo_k_is_lte(int64_t K) { return K >= TURBO_K_MIN && K <= TURBO_K_MAX && turbo_k_next(K) == K; }
+struct TbSeg {               // the segmentation of one transport block, in bytes (everything is a multiple of 8 bits)
+    int A8, L8;              // payload bytes; 3 with a CRC24B per block, else 0
+    int C, Cm;               // code blocks; the first Cm of them have Km8 bytes, the rest Kp8
+    int Km8, Kp8, F8;        // F8 filler bytes in front of block 0
+};
+struct TbRange {             // blocks first .. first + count - 1 of every transport block: dense [n_tb][count][kbytes] packed bits at ws + base
+    int first, count, kbytes;
+    int64_t base;
+};
+struct TbSegArgs {           // tb_segment_kernel (payload_in -> ws) and tb_desegment_kernel (ws -> the outputs that are not null)
+    TbSeg g;
+    int n_ranges;            // <= 3, in block order, tiling 0 .. C
+    TbRange range[3];
+    int64_t n_tb;
+    uint8_t* ws;
+    int payload_mode;        // ofdm_bits_mode of payload_in / payload_out: dense [n_tb][A] or [n_tb][A/8]
+    const uint8_t* payload_in;
+    uint8_t* payload_out;
+    uint8_t* tb_ok;          // [n_tb]
+    uint8_t* cb_ok;          // [n_tb][C]
+    uint32_t* syndrome;      // [n_tb]
+};
+struct TbConcatArgs {        // group g of every transport block: bits[g] bytes (one bit each) at ws + base[g] + t*bits[g] -> codeword bit off[g] ..
+    int n_groups;
+    int64_t bits[3], off[3], base[3];
+    int64_t n_tb, G, cw_bits;
+    const uint8_t* ws;
+    uint8_t* cw;             // [n_tb][cw_bits] or [n_tb][cw_bits / 8]; zeros from G on
+    int cw_mode;
+};
+hipError_t launch_tb_segment(const TbSegArgs& a, hipStream_t s);
+hipError_t launch_tb_desegment(const TbSegArgs& a, hipStream_t s);
+hipError_t launch_tb_concat(const TbConcatArgs& a, hipStream_t s);
+hipError_t tb_prepare();                 // loads the three kernels (before a stream capture)
+uint32_t crc_long_host(int kind, const uint8_t* bits_packed, int64_t n_bytes);   // the kernels' chunk-and-combine routine on the host
+
 hipError_t launch_rx_demod(const RxDev& rx, const DemodArgs& a, hipStream_t s);
 hipError_t launch_rx_sync(const RxDev& rx, const SyncArgs& a, hipStream_t s);
 // batch CFO receiver: one wave per frame walks the trial table in order (gate, distance rule, 101st sync) -> FoDecideArgs outputs

@@ -98,6 +98,24 @@ class TurboOut(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("llr", C.c_void_p)]
 
 
+class TbGroup(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("K", C.c_int32), ("E", C.c_int32), ("cw_bit_offset", C.c_int64),
+                ("soft_offset", C.c_int64)]
+
+
+class TbGeom(C.Structure):
+    """ofdm_tb_geom: segmentation, rate-matching sizes and groups of one transport block."""
+    _fields_ = [(n, C.c_int32) for n in ("A", "Z", "B", "L", "C", "K_plus", "K_minus", "C_plus", "C_minus", "F", "n_groups", "G", "q",
+                                         "gamma", "E0", "E1", "Ncb_minus", "Ncb_plus")] + [("group", TbGroup * 3),
+                                                                                           ("soft_floats", C.c_int64)]
+
+
+class TbOut(C.Structure):
+    """ofdm_tb_out: device pointers of the transport-block decoder (None = not wanted)."""
+    _fields_ = [("payload", C.c_void_p), ("payload_mode", C.c_int32), ("tb_ok", C.c_void_p), ("cb_ok", C.c_void_p),
+                ("syndrome", C.c_void_p)]
+
+
 class TrkCfg(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("cp_len", C.c_int32), ("num_synch_bins", C.c_int32), ("num_data_bins", C.c_int32),
                 ("synch_D", C.c_int32), ("rows_sync", C.c_int32), ("rows_data", C.c_int32), ("zc_root", C.c_int32),
@@ -185,6 +203,17 @@ PROTOTYPES = {
                                                  C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "ofdm_tx_reserve_turbo_rm": (C.c_int, [C.c_void_p]),
     "ofdm_rx_reserve_turbo_rm": (C.c_int, [C.c_void_p]),
+    "ofdm_turbo_k_next": (C.c_int32, [C.c_int32]),
+    "ofdm_tb_geometry": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.POINTER(TbGeom)]),
+    "ofdm_crc_compute_long": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_uint32)]),
+    "ofdm_tx_tb_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_int32, C.c_int64, C.c_void_p]),
+    "ofdm_tb_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                        C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_int64, C.POINTER(TbOut), C.c_void_p]),
+    "ofdm_tx_reserve_tb": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
+    "ofdm_rx_reserve_tb": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

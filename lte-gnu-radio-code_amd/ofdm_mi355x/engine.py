@@ -128,6 +128,33 @@ def crc_compute(kind: int, bits_packed, A: int | None = None) -> int:
     return int(crc.value)
 
 
+def crc_compute_long(kind: int, bits_packed, n_bits: int | None = None) -> int:
+    """ofdm_crc_compute_long: crc_compute for up to 2^30 bits, through the kernels' chunk-and-combine routine; host arithmetic."""
+    buf = np.ascontiguousarray(bits_packed, dtype=np.uint8)
+    n_bits = 8 * buf.size if n_bits is None else int(n_bits)
+    if n_bits > 8 * buf.size:
+        raise ValueError("crc_compute_long: %d bits from %d bytes" % (n_bits, buf.size))
+    crc = C.c_uint32(0)
+    check(_lib.load().ofdm_crc_compute_long(int(kind), ptr(buf), n_bits, C.byref(crc)))
+    return int(crc.value)
+
+
+def turbo_k_next(bits: int) -> int:
+    """ofdm_turbo_k_next: the smallest of LTE's 188 turbo block sizes that holds `bits` bits."""
+    return int(check(_lib.load().ofdm_turbo_k_next(int(bits))))
+
+
+def tb_geometry(A: int, Z: int = 0, G: int = 0, q: int = 1, N_IR: int = 0) -> dict:
+    """ofdm_tb_geometry: segmentation of a transport block of A bits at maximum block size Z (0 = 6144), and with G > 0 the
+    rate-matching sizes for G coded bits in units of q under the soft-buffer limit N_IR (0 = none); host arithmetic.  A dict of
+    the fields of ofdm_tb_geom, `groups` a list of dicts (first, count, K, E, cw_bit_offset, soft_offset)."""
+    g = _lib.TbGeom()
+    check(_lib.load().ofdm_tb_geometry(int(A), int(Z), int(G), int(q), int(N_IR), C.byref(g)))
+    out = {n: int(getattr(g, n)) for n, _ in _lib.TbGeom._fields_ if n != "group"}
+    out["groups"] = [{n: int(getattr(g.group[i], n)) for n, _ in _lib.TbGroup._fields_} for i in range(g.n_groups)]
+    return out
+
+
 def gold_bits(c_init: int, first: int, n: int) -> np.ndarray:
     """ofdm_gold_bits: c(first .. first + n - 1) of TS 36.211 7.2 for c_init, one bit per byte; host arithmetic, random access."""
     out = np.empty(max(int(n), 0), np.uint8)
@@ -345,6 +372,26 @@ class RxEngine:
         check(self.lib.ofdm_turbo_rate_dematch_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                       int(E), int(Ncb), int(rv), ptr(d_rv), int(bool(accumulate)), ptr(d_out),
                                                       int(out_stride), ptr(stream)))
+
+    # ---- transport-block layer (TS 36.212 5.1.1, 5.1.2, 5.1.5): de-match per group, decode per K, desegment ----
+    def reserve_tb(self, n_tb: int, A: int, Z: int = 0):
+        """Sizes the workspaces (this layer's and the turbo decoder's) for n_tb transport blocks of A bits per call and loads
+        the kernels (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_tb(self._h, int(n_tb), int(A), int(Z)))
+
+    def tb_decode_frames(self, d_llr, n_tb, llr_stride, A, G, qpp_plus, d_soft, soft_stride, n_iter, qpp_minus=(0, 0), Z=0, q=1,
+                         N_IR=0, rv=0, d_rv=None, accumulate=False, d_payload=None, payload_mode=BITS_UNPACKED, d_tb_ok=None,
+                         d_cb_ok=None, d_syndrome=None, stream=None):
+        """ofdm_tb_decode_frames: the G LLRs of transport block t at d_llr + t*llr_stride -> its HARQ soft buffer at
+        d_soft + t*soft_stride (written, or added to with accumulate) -> payload [n_tb][A], tb_ok [n_tb], cb_ok [n_tb][C],
+        syndrome [n_tb] (each only where given).  qpp_plus / qpp_minus: (f1, f2) for K+ and K- of tb_geometry(A, Z)."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TbOut(addr(d_payload), int(payload_mode), addr(d_tb_ok), addr(d_cb_ok), addr(d_syndrome))
+        check(self.lib.ofdm_tb_decode_frames(self._h, ptr(d_llr), int(n_tb), int(llr_stride), int(A), int(Z), int(G), int(q), int(N_IR),
+                                             int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]), int(rv), ptr(d_rv),
+                                             int(n_iter), int(bool(accumulate)), ptr(d_soft), int(soft_stride), C.byref(out), ptr(stream)))
 
     # ---- Gold-sequence descrambling in front of the decoder, CRC check behind it (TS 36.211 7.2, TS 36.212 5.1.1) ----
     def reserve_bitproc(self):
@@ -584,6 +631,21 @@ class TxEngine:
         check(self.lib.ofdm_tx_turbo_encode_rm_frames(self._h, ptr(d_info), int(info_mode), int(n_seg), int(blocks_per_seg), int(K),
                                                       int(f1), int(f2), int(E), int(Ncb), int(rv), ptr(d_rv), ptr(d_coded),
                                                       int(coded_mode), int(seg_bits), ptr(stream)))
+
+    # ---- transport-block layer (TS 36.212 5.1.1, 5.1.2, 5.1.5): segment, encode per group, concatenate ----
+    def reserve_tb(self, n_tb: int, A: int, G: int, Z: int = 0, q: int = 1):
+        """Sizes the workspace for n_tb transport blocks of A bits in G coded bits per call and loads the kernels (before a graph
+        capture)."""
+        check(self.lib.ofdm_tx_reserve_tb(self._h, int(n_tb), int(A), int(Z), int(G), int(q)))
+
+    def tb_encode_frames(self, d_payload, n_tb, A, G, qpp_plus, d_cw, cw_bits, qpp_minus=(0, 0), Z=0, q=1, N_IR=0, rv=0, d_rv=None,
+                         payload_mode=BITS_UNPACKED, cw_mode=BITS_UNPACKED, stream=None):
+        """ofdm_tx_tb_encode_frames: d_payload dense [n_tb][A] bits -> CRC24A, segmentation at Z (0 = 6144) with CRC24B per code
+        block, turbo coding and rate matching to G bits (units of q, redundancy version rv or d_rv per transport block, soft-buffer
+        limit N_IR), concatenated into d_cw [n_tb][cw_bits].  qpp_plus / qpp_minus: (f1, f2) for K+ and K- of tb_geometry(A, Z)."""
+        check(self.lib.ofdm_tx_tb_encode_frames(self._h, ptr(d_payload), int(payload_mode), int(n_tb), int(A), int(Z), int(G), int(q),
+                                                int(N_IR), int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]),
+                                                int(rv), ptr(d_rv), ptr(d_cw), int(cw_mode), int(cw_bits), ptr(stream)))
 
     # ---- CRC attach in front of the encoder, Gold-sequence scrambling behind it (TS 36.212 5.1.1, TS 36.211 7.2) ----
     def reserve_bitproc(self):
