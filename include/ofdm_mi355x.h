@@ -526,6 +526,33 @@ int ofdm_rx_reserve_turbo(ofdm_rx* h, int64_t n_blocks, int32_t K);
  * count, a batch beyond the kernel's index range) return OFDM_ERR_INVALID before anything is enqueued. */
 int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
                              int32_t f1, int32_t f2, int32_t n_iter, const ofdm_turbo_out* out, void* stream);
+/* Early termination by CRC: a second decoder entry point for code blocks that end in a CRC (every code block of a transport
+ * block does).  After every full iteration from min_iter on, the CRC of each block's hard decisions is checked; a block that
+ * passes stops there.  It changes no arithmetic: with bit_n[k] and llr_n[k] the outputs of ofdm_turbo_decode_frames at
+ * n_iter = n on the same 3K + 12 LLRs,
+ *   block b stops at the smallest n in min_iter .. max_iter for which bit_n[0] D^(K-1) + .. + bit_n[K-1] is divisible by the
+ *   generator of crc_kind -- the arithmetic of the CRC block above: all four kinds, zero mask, all K bits, so that leading zeros
+ *   (filler) do not matter -- and at max_iter if there is no such n;
+ *   bits and llr are bit_n and llr_n (floats by bit pattern), iters = n, crc_ok = 1 iff the remainder was zero at n.
+ * False passes are part of the contract: a wrong decision whose remainder is zero stops the block, and a block of all-zero or
+ * all-NaN LLRs decides all zeros and stops at min_iter with crc_ok = 1.  1 <= min_iter <= max_iter <= 16; stat_stride is 0 or
+ * >= blocks_per_seg.  The layout, no-op (an `out` without any of its four pointers) and error rules are those of
+ * ofdm_turbo_decode_frames, an unknown crc_kind included: OFDM_ERR_INVALID before anything is enqueued, and likewise inside a
+ * capture for a call that would have to grow the workspace.  One launch, no host synchronisation, no allocation once reserved.
+ * Deterministic: a block's outputs depend on its own LLRs only, in any batch, at any stride, next to any neighbours (a wave of 8
+ * blocks runs as long as its slowest block; the others are frozen, not re-decoded). */
+typedef struct ofdm_turbo_es_out {   /* DEVICE pointers; NULL = not wanted */
+    uint8_t* bits;  int32_t bits_mode;  float* llr;      /* as ofdm_turbo_out */
+    uint8_t* iters;        /* iterations the block ran, min_iter .. max_iter                      */
+    uint8_t* crc_ok;       /* 1 iff the remainder was zero after that iteration                   */
+    int64_t  stat_stride;  /* iters / crc_ok of block (s, b) at s*stat_stride + b; 0 = blocks_per_seg */
+} ofdm_turbo_es_out;
+/* ofdm_rx_reserve_turbo for this entry point: the same workspace (one per handle, it only grows) with a second array of
+ * 4 n_blocks K bytes, the a-posteriori values of each block's latest checked iteration. */
+int ofdm_rx_reserve_turbo_es(ofdm_rx* h, int64_t n_blocks, int32_t K);
+int ofdm_turbo_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
+                                int32_t K, int32_t f1, int32_t f2, int32_t crc_kind, int32_t min_iter, int32_t max_iter,
+                                const ofdm_turbo_es_out* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------ rate matching (LTE turbo)
  * The three sub-block interleavers, the circular buffer with its limit Ncb and the redundancy versions of TS 36.212 5.1.4.1
@@ -666,6 +693,20 @@ int ofdm_tb_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t 
  * load the kernels; the workspaces only grow.  Growing waits for the device, so call these before capturing into a hipGraph. */
 int ofdm_tx_reserve_tb(ofdm_tx* h, int64_t n_tb, int32_t A, int32_t Z, int64_t G, int32_t q);
 int ofdm_rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z);
+/* ofdm_tb_decode_frames with early termination: the same sequence, the decoder launches through ofdm_turbo_decode_es_frames
+ * with crc_kind = OFDM_CRC24B when L = 24 and OFDM_CRC24A when C = 1 (the block then ends in the transport block's own CRC).
+ * cb_iters[t][r] = the iterations block r ran.  payload, tb_ok, cb_ok and syndrome are those of ofdm_tb_decode_frames run with
+ * each block at its own n; the soft buffer is written by the de-matcher only.  cb_iters alone makes the call decode.
+ * ofdm_rx_reserve_tb_es is ofdm_rx_reserve_tb with the decoder workspace of ofdm_rx_reserve_turbo_es. */
+typedef struct ofdm_tb_es_out {  /* DEVICE pointers; NULL = not wanted */
+    uint8_t*  payload;  int32_t payload_mode;  uint8_t* tb_ok;  uint8_t* cb_ok;  uint32_t* syndrome;   /* as ofdm_tb_out */
+    uint8_t*  cb_iters;      /* [n_tb][C]                                                                       */
+} ofdm_tb_es_out;
+int ofdm_tb_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t llr_stride, int32_t A, int32_t Z, int64_t G,
+                             int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus, int32_t f2_plus,
+                             int32_t rv, const int32_t* d_rv, int32_t min_iter, int32_t max_iter, int32_t accumulate,
+                             float* d_soft, int64_t soft_stride, const ofdm_tb_es_out* out, void* stream);
+int ofdm_rx_reserve_tb_es(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z);
 
 /* ------------------------------------------------------- CFO-search receiver */
 /* Replaces OFDMReceiver.SynchEstAndFO (G/LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py:28-369): the

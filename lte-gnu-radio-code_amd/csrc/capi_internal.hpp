@@ -94,7 +94,8 @@ struct ofdm_rx {
     float p_kbar = 0.f, p_inv_skk = 0.f;
     cf* f_usum = nullptr;                // [n_seg][rows] pilot sums of ofdm_pilot_track_frames (read by the cfo launch)
     int64_t cap_usum = 0;
-    // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints
+    // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
+    // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;
     int64_t cap_turbo = 0;               // floats
     // ---- transport-block layer (ofdm_rx_reserve_tb): the decoder's packed bits, dense [n_tb][count][K / 8] per K

@@ -127,6 +127,11 @@ int64_t rx_turbo_floats(const ofdm_tb_geom& g, int64_t n_tb) {
     return g.C_minus ? std::max(p, turbo_ws_floats(n_tb * g.C_minus, g.K_minus)) : p;
 }
 
+int64_t rx_turbo_es_floats(const ofdm_tb_geom& g, int64_t n_tb) {
+    const int64_t p = turbo_es_ws_floats(n_tb * g.C_plus, g.K_plus);
+    return g.C_minus ? std::max(p, turbo_es_ws_floats(n_tb * g.C_minus, g.K_minus)) : p;
+}
+
 template <class H>
 int tb_grow(H* h, int64_t bytes) {
     if (bytes <= h->cap_tb) return OFDM_OK;
@@ -137,6 +142,103 @@ int tb_grow(H* h, int64_t bytes) {
     const int rc = dev_alloc(&h->tb_ws, size_t(bytes));
     if (rc != OFDM_OK) return rc;
     h->cap_tb = bytes;
+    return OFDM_OK;
+}
+
+int rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z, bool es, const char* who) {
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    ofdm_tb_geom g;
+    const char* bad = tb_plan(A, Z, 0, 0, 0, &g);
+    if (!*bad && (n_tb < 0 || n_tb > TBCC_MAX_BLOCKS / g.C || (n_tb > 0 && g.soft_floats > TB_MAX_ITEMS / n_tb)))
+        bad = "negative count or a batch beyond the kernels' index range";
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(tb_prepare());
+    HIP_TRY(turbo_rm_prepare());
+    auto reserve = es ? ofdm_rx_reserve_turbo_es : ofdm_rx_reserve_turbo;
+    int rc = OFDM_OK;
+    if (g.C_minus) rc = reserve(h, n_tb * g.C_minus, g.K_minus);
+    if (rc == OFDM_OK) rc = reserve(h, n_tb * g.C_plus, g.K_plus);
+    return rc != OFDM_OK ? rc : tb_grow(h, rx_layout(g, n_tb).bytes);
+}
+
+// what tells ofdm_tb_decode_frames (min_iter == max_iter == n_iter through the fixed decoder) from ofdm_tb_decode_es_frames
+struct TbDecode {
+    const char* who;
+    const char* reserve_name;
+    bool es;
+    int32_t min_iter, max_iter;
+    uint8_t* cb_iters;       // [n_tb][C], or null
+};
+
+int tb_decode(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t llr_stride, int32_t A, int32_t Z, int64_t G, int32_t q, int64_t N_IR,
+              int32_t f1_minus, int32_t f2_minus, int32_t f1_plus, int32_t f2_plus, int32_t rv, const int32_t* d_rv, const TbDecode& d,
+              int32_t accumulate, float* d_soft, int64_t soft_stride, const ofdm_tb_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", d.who);
+    ofdm_tb_geom g;
+    const char* bad = tb_bad_call(n_tb, A, Z, G, q, N_IR, f1_minus, f2_minus, f1_plus, f2_plus, rv, d_rv, llr_stride, soft_stride, &g);
+    if (!*bad) {
+        if (!d.es && (d.max_iter < 1 || d.max_iter > TURBO_ITER_MAX)) bad = "n_iter must lie in 1 .. 16";
+        else if (d.es && (d.min_iter < 1 || d.max_iter > TURBO_ITER_MAX || d.min_iter > d.max_iter)) bad = "1 <= min_iter <= max_iter <= 16 does not hold";
+        else if (llr_stride < G) bad = "llr_stride < G";
+        else if (soft_stride < g.soft_floats) bad = "soft_stride < sum (3 K_r + 12)";
+        else if (!out) bad = "null out";
+        else if (out->payload && !tbcc_bits_mode_ok(out->payload_mode)) bad = "payload_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+    }
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", d.who, bad);
+    if (n_tb == 0) return OFDM_OK;
+    if (!d_llr || !d_soft) return fail(OFDM_ERR_INVALID, "%s: null buffer", d.who);
+    const bool decode = out->payload || out->tb_ok || out->cb_ok || out->syndrome || d.cb_iters;
+    hipStream_t s = pick_stream(h, stream);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    const RxLayout l = rx_layout(g, n_tb);
+    if (decode && (l.bytes > h->cap_tb || (d.es ? rx_turbo_es_floats(g, n_tb) : rx_turbo_floats(g, n_tb)) > h->cap_turbo)) {
+        int rc = refuse_growth_in_capture(s, d.who, d.reserve_name);
+        if (rc == OFDM_OK) rc = rx_reserve_tb(h, n_tb, A, Z, d.es, d.reserve_name);
+        if (rc != OFDM_OK) return rc;
+    }
+    for (int i = 0; i < g.n_groups; ++i) {
+        const auto& x = g.group[i];
+        const int rc = ofdm_turbo_rate_dematch_frames(h, d_llr + x.cw_bit_offset, n_tb, llr_stride, x.count, x.K, x.E,
+                                                      x.first < g.C_minus ? g.Ncb_minus : g.Ncb_plus, rv, d_rv, accumulate,
+                                                      d_soft + x.soft_offset, soft_stride, s);
+        if (rc != OFDM_OK) return rc;
+    }
+    if (!decode) return OFDM_OK;
+    TbSegArgs sa{};
+    sa.g = tb_seg(g);
+    for (int which = 0; which < 2; ++which) {
+        const int count = which ? g.C_plus : g.C_minus, K = which ? g.K_plus : g.K_minus;
+        if (!count) continue;
+        const int first = which ? g.C_minus : 0;
+        const float* soft = d_soft + (which ? int64_t(g.C_minus) * (3 * int64_t(g.K_minus) + 12) : 0);
+        const int32_t f1 = which ? f1_plus : f1_minus, f2 = which ? f2_plus : f2_minus;
+        int rc;
+        if (d.es) {
+            ofdm_turbo_es_out to{};
+            to.bits = h->tb_ws + l.bits[which];
+            to.bits_mode = OFDM_BITS_PACKED;
+            to.iters = d.cb_iters ? d.cb_iters + first : nullptr;
+            to.stat_stride = g.C;
+            rc = ofdm_turbo_decode_es_frames(h, soft, n_tb, soft_stride, count, K, f1, f2, g.L ? OFDM_CRC24B : OFDM_CRC24A, d.min_iter,
+                                             d.max_iter, &to, s);
+        } else {
+            ofdm_turbo_out to{};
+            to.bits = h->tb_ws + l.bits[which];
+            to.bits_mode = OFDM_BITS_PACKED;
+            rc = ofdm_turbo_decode_frames(h, soft, n_tb, soft_stride, count, K, f1, f2, d.max_iter, &to, s);
+        }
+        if (rc != OFDM_OK) return rc;
+        sa.range[sa.n_ranges++] = TbRange{first, count, K >> 3, l.bits[which]};
+    }
+    sa.n_tb = n_tb;
+    sa.ws = h->tb_ws;
+    sa.payload_mode = out->payload_mode;
+    sa.payload_out = out->payload;
+    sa.tb_ok = out->tb_ok;
+    sa.cb_ok = out->cb_ok;
+    sa.syndrome = out->syndrome;
+    HIP_TRY(launch_tb_desegment(sa, s));
     return OFDM_OK;
 }
 
@@ -176,21 +278,8 @@ int ofdm_tx_reserve_tb(ofdm_tx* h, int64_t n_tb, int32_t A, int32_t Z, int64_t G
     return tb_grow(h, tx_layout(g, n_tb).bytes);
 }
 
-int ofdm_rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tb: null handle");
-    ofdm_tb_geom g;
-    const char* bad = tb_plan(A, Z, 0, 0, 0, &g);
-    if (!*bad && (n_tb < 0 || n_tb > TBCC_MAX_BLOCKS / g.C || (n_tb > 0 && g.soft_floats > TB_MAX_ITEMS / n_tb)))
-        bad = "negative count or a batch beyond the kernels' index range";
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tb: %s", bad);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(tb_prepare());
-    HIP_TRY(turbo_rm_prepare());
-    int rc = OFDM_OK;
-    if (g.C_minus) rc = ofdm_rx_reserve_turbo(h, n_tb * g.C_minus, g.K_minus);
-    if (rc == OFDM_OK) rc = ofdm_rx_reserve_turbo(h, n_tb * g.C_plus, g.K_plus);
-    return rc != OFDM_OK ? rc : tb_grow(h, rx_layout(g, n_tb).bytes);
-}
+int ofdm_rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z) { return rx_reserve_tb(h, n_tb, A, Z, false, "ofdm_rx_reserve_tb"); }
+int ofdm_rx_reserve_tb_es(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z) { return rx_reserve_tb(h, n_tb, A, Z, true, "ofdm_rx_reserve_tb_es"); }
 
 int ofdm_tx_tb_encode_frames(ofdm_tx* h, const uint8_t* d_payload, int32_t payload_mode, int64_t n_tb, int32_t A, int32_t Z,
                              int64_t G, int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus,
@@ -248,59 +337,20 @@ int ofdm_tb_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t 
                           int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus, int32_t f2_plus,
                           int32_t rv, const int32_t* d_rv, int32_t n_iter, int32_t accumulate, float* d_soft, int64_t soft_stride,
                           const ofdm_tb_out* out, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tb_decode_frames: null handle");
-    ofdm_tb_geom g;
-    const char* bad = tb_bad_call(n_tb, A, Z, G, q, N_IR, f1_minus, f2_minus, f1_plus, f2_plus, rv, d_rv, llr_stride, soft_stride, &g);
-    if (!*bad) {
-        if (n_iter < 1 || n_iter > TURBO_ITER_MAX) bad = "n_iter must lie in 1 .. 16";
-        else if (llr_stride < G) bad = "llr_stride < G";
-        else if (soft_stride < g.soft_floats) bad = "soft_stride < sum (3 K_r + 12)";
-        else if (!out) bad = "null out";
-        else if (out->payload && !tbcc_bits_mode_ok(out->payload_mode)) bad = "payload_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-    }
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tb_decode_frames: %s", bad);
-    if (n_tb == 0) return OFDM_OK;
-    if (!d_llr || !d_soft) return fail(OFDM_ERR_INVALID, "ofdm_tb_decode_frames: null buffer");
-    const bool decode = out->payload || out->tb_ok || out->cb_ok || out->syndrome;
-    hipStream_t s = pick_stream(h, stream);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    const RxLayout l = rx_layout(g, n_tb);
-    if (decode && (l.bytes > h->cap_tb || rx_turbo_floats(g, n_tb) > h->cap_turbo)) {
-        int rc = refuse_growth_in_capture(s, "ofdm_tb_decode_frames", "ofdm_rx_reserve_tb");
-        if (rc == OFDM_OK) rc = ofdm_rx_reserve_tb(h, n_tb, A, Z);
-        if (rc != OFDM_OK) return rc;
-    }
-    for (int i = 0; i < g.n_groups; ++i) {
-        const auto& x = g.group[i];
-        const int rc = ofdm_turbo_rate_dematch_frames(h, d_llr + x.cw_bit_offset, n_tb, llr_stride, x.count, x.K, x.E,
-                                                      x.first < g.C_minus ? g.Ncb_minus : g.Ncb_plus, rv, d_rv, accumulate,
-                                                      d_soft + x.soft_offset, soft_stride, s);
-        if (rc != OFDM_OK) return rc;
-    }
-    if (!decode) return OFDM_OK;
-    TbSegArgs sa{};
-    sa.g = tb_seg(g);
-    for (int which = 0; which < 2; ++which) {
-        const int count = which ? g.C_plus : g.C_minus, K = which ? g.K_plus : g.K_minus;
-        if (!count) continue;
-        const int first = which ? g.C_minus : 0;
-        ofdm_turbo_out to{};
-        to.bits = h->tb_ws + l.bits[which];
-        to.bits_mode = OFDM_BITS_PACKED;
-        const int rc = ofdm_turbo_decode_frames(h, d_soft + (which ? int64_t(g.C_minus) * (3 * int64_t(g.K_minus) + 12) : 0), n_tb, soft_stride,
-                                                count, K, which ? f1_plus : f1_minus, which ? f2_plus : f2_minus, n_iter, &to, s);
-        if (rc != OFDM_OK) return rc;
-        sa.range[sa.n_ranges++] = TbRange{first, count, K >> 3, l.bits[which]};
-    }
-    sa.n_tb = n_tb;
-    sa.ws = h->tb_ws;
-    sa.payload_mode = out->payload_mode;
-    sa.payload_out = out->payload;
-    sa.tb_ok = out->tb_ok;
-    sa.cb_ok = out->cb_ok;
-    sa.syndrome = out->syndrome;
-    HIP_TRY(launch_tb_desegment(sa, s));
-    return OFDM_OK;
+    TbDecode d{"ofdm_tb_decode_frames", "ofdm_rx_reserve_tb", false, n_iter, n_iter, nullptr};
+    return tb_decode(h, d_llr, n_tb, llr_stride, A, Z, G, q, N_IR, f1_minus, f2_minus, f1_plus, f2_plus, rv, d_rv, d, accumulate, d_soft,
+                     soft_stride, out, stream);
+}
+
+int ofdm_tb_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t llr_stride, int32_t A, int32_t Z, int64_t G,
+                             int32_t q, int64_t N_IR, int32_t f1_minus, int32_t f2_minus, int32_t f1_plus, int32_t f2_plus,
+                             int32_t rv, const int32_t* d_rv, int32_t min_iter, int32_t max_iter, int32_t accumulate, float* d_soft,
+                             int64_t soft_stride, const ofdm_tb_es_out* out, void* stream) {
+    TbDecode d{"ofdm_tb_decode_es_frames", "ofdm_rx_reserve_tb_es", true, min_iter, max_iter, out ? out->cb_iters : nullptr};
+    ofdm_tb_out o{};
+    if (out) o = ofdm_tb_out{out->payload, out->payload_mode, out->tb_ok, out->cb_ok, out->syndrome};
+    return tb_decode(h, d_llr, n_tb, llr_stride, A, Z, G, q, N_IR, f1_minus, f2_minus, f1_plus, f2_plus, rv, d_rv, d, accumulate, d_soft,
+                     soft_stride, out ? &o : nullptr, stream);
 }
 
 }  // extern "C"

@@ -31,6 +31,25 @@ int turbo_ensure(ofdm_rx* h, int64_t n_blocks, int32_t K, hipStream_t s) {
     const int rc = refuse_growth_in_capture(s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo");
     return rc != OFDM_OK ? rc : ofdm_rx_reserve_turbo(h, n_blocks, K);
 }
+// both decoders share the handle's workspace: it holds `need` floats afterwards, and only grows
+int turbo_grow(ofdm_rx* h, int64_t need) {
+    if (need <= h->cap_turbo) return OFDM_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipDeviceSynchronize());
+    free_dev(&h->t_ws);
+    h->cap_turbo = 0;
+    const int rc = dev_alloc(&h->t_ws, size_t(need));
+    if (rc != OFDM_OK) return rc;
+    h->cap_turbo = need;
+    return OFDM_OK;
+}
+const char* turbo_bad_reserve(int64_t n_blocks, int32_t K) {
+    if (!turbo_valid_k(K)) return TURBO_BAD_K;
+    if (n_blocks < 0) return "negative count";
+    if (n_blocks > TBCC_MAX_BLOCKS) return "batch beyond the kernel's index range";
+    return "";
+}
+bool turbo_es_wanted(const ofdm_turbo_es_out* o) { return o && (o->bits || o->llr || o->iters || o->crc_ok); }
 }  // namespace
 
 extern "C" {
@@ -77,21 +96,11 @@ int ofdm_tx_turbo_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_
 // the device, so it cannot happen inside a capture: ofdm_turbo_decode_frames refuses there and names this call.
 int ofdm_rx_reserve_turbo(ofdm_rx* h, int64_t n_blocks, int32_t K) {
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: null handle");
-    if (!turbo_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: %s", TURBO_BAD_K);
-    if (n_blocks < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: negative count");
-    if (n_blocks > TBCC_MAX_BLOCKS) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: batch beyond the kernel's index range");
+    const char* bad = turbo_bad_reserve(n_blocks, K);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo: %s", bad);
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(turbo_decode_prepare());
-    const int64_t need = turbo_ws_floats(n_blocks, K);
-    if (need <= h->cap_turbo) return OFDM_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->t_ws);
-    h->cap_turbo = 0;
-    const int rc = dev_alloc(&h->t_ws, size_t(need));
-    if (rc != OFDM_OK) return rc;
-    h->cap_turbo = need;
-    return OFDM_OK;
+    return turbo_grow(h, turbo_ws_floats(n_blocks, K));
 }
 
 int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
@@ -125,6 +134,63 @@ int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int6
     a.llr_out = out->llr;
     a.q = turbo_qpp(K, f1, f2);
     HIP_TRY(launch_turbo_decode(a, s));
+    return OFDM_OK;
+}
+
+// ---- early termination by CRC: the same workspace with a second K-float array per block
+int ofdm_rx_reserve_turbo_es(ofdm_rx* h, int64_t n_blocks, int32_t K) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo_es: null handle");
+    const char* bad = turbo_bad_reserve(n_blocks, K);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo_es: %s", bad);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(turbo_decode_es_prepare());
+    return turbo_grow(h, turbo_es_ws_floats(n_blocks, K));
+}
+
+int ofdm_turbo_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
+                                int32_t f1, int32_t f2, int32_t crc_kind, int32_t min_iter, int32_t max_iter,
+                                const ofdm_turbo_es_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_es_frames: null handle");
+    const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
+    if (!*bad) {
+        if (crc_kind < OFDM_CRC24A || crc_kind > OFDM_CRC8) bad = "crc_kind must be OFDM_CRC24A, OFDM_CRC24B, OFDM_CRC16 or OFDM_CRC8";
+        else if (min_iter < 1 || max_iter > TURBO_ITER_MAX || min_iter > max_iter) bad = "1 <= min_iter <= max_iter <= 16 does not hold";
+        else if (seg_stride < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_stride < blocks_per_seg * (3K + 12)";
+        else if (!tbcc_items_ok(n_seg, seg_stride)) bad = "batch beyond the kernel's index range";
+        else if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode)) bad = "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else if (out && out->stat_stride != 0 && out->stat_stride < blocks_per_seg) bad = "stat_stride must be 0 or >= blocks_per_seg";
+        else if (out && !tbcc_items_ok(n_seg, out->stat_stride)) bad = "batch beyond the kernel's index range";
+    }
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_es_frames: %s", bad);
+    if (n_seg == 0 || blocks_per_seg == 0 || !turbo_es_wanted(out)) return OFDM_OK;
+    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_es_frames: null d_llr");
+    hipStream_t s = pick_stream(h, stream);
+    const int64_t n_blocks = n_seg * blocks_per_seg;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    if (turbo_es_ws_floats(n_blocks, K) > h->cap_turbo) {
+        int rc = refuse_growth_in_capture(s, "ofdm_turbo_decode_es_frames", "ofdm_rx_reserve_turbo_es");
+        if (rc == OFDM_OK) rc = ofdm_rx_reserve_turbo_es(h, n_blocks, K);
+        if (rc != OFDM_OK) return rc;
+    }
+    TurboDecEsArgs a{};
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_blocks;
+    a.blocks_per_seg = blocks_per_seg;
+    a.min_iter = min_iter;
+    a.max_iter = max_iter;
+    a.crc_kind = crc_kind;
+    a.ext = h->t_ws;
+    a.post = a.ext + n_blocks * K;
+    a.ckpt = a.post + n_blocks * K;
+    a.bits = out->bits;
+    a.bits_mode = out->bits_mode;
+    a.llr_out = out->llr;
+    a.iters = out->iters;
+    a.crc_ok = out->crc_ok;
+    a.stat_stride = out->stat_stride ? out->stat_stride : blocks_per_seg;
+    a.q = turbo_qpp(K, f1, f2);
+    HIP_TRY(launch_turbo_decode_es(a, s));
     return OFDM_OK;
 }
 

@@ -342,6 +342,29 @@ hipError_t launch_turbo_encode(const TurboEncArgs& a, hipStream_t s);
 hipError_t launch_turbo_decode(const TurboDecArgs& a, hipStream_t s);
 hipError_t turbo_decode_prepare();       // loads the decoder's code object (before a stream capture)
 
+// ---- turbo decoder with early termination by CRC (turbo_es.hip; contract: include/ofdm_mi355x.h)
+struct TurboDecEsArgs {
+    const float* llr;        // as TurboDecArgs
+    int64_t seg_stride;
+    int64_t n_blocks;
+    int blocks_per_seg;
+    int min_iter, max_iter;  // 1 <= min_iter <= max_iter <= TURBO_ITER_MAX
+    int crc_kind;            // ofdm_crc_kind of the stop check: zero mask, all K bits
+    float* ext;              // workspace [n_blocks][K]: the extrinsic values
+    float* post;             // workspace [n_blocks][K]: post of the block's latest stop-eligible iteration, natural order
+    float* ckpt;             // workspace [waves][ceil(K / TURBO_CKPT)][64]
+    uint8_t* bits;           // dense [n_blocks][K] bits, or null
+    int bits_mode;
+    float* llr_out;          // dense [n_blocks][K], or null
+    uint8_t* iters;          // block (seg, b) at seg*stat_stride + b, or null
+    uint8_t* crc_ok;         // likewise
+    int64_t stat_stride;     // resolved (not 0)
+    TurboQpp q;
+};
+int64_t turbo_es_ws_floats(int64_t n_blocks, int K);         // ext + post + ckpt, in this order
+hipError_t launch_turbo_decode_es(const TurboDecEsArgs& a, hipStream_t s);
+hipError_t turbo_decode_es_prepare();    // loads the kernel (before a stream capture)
+
 // ---- turbo rate matching (turbo_rm.hip; TS 36.212 5.1.4.1; contract: include/ofdm_mi355x.h)
 constexpr int TURBO_RM_MAX_COPIES = 16;  // E <= 16 Navail
 struct TurboRmGeom {         // what the closed form of the sub-block interleavers and the circular buffer needs, all of it from K, E, Ncb

@@ -16,6 +16,8 @@
 
 #pragma clang fp contract(off)
 
+#include "turbo_siso.hpp"
+
 namespace ofdm {
 
 namespace {
@@ -148,27 +150,15 @@ __global__ void __launch_bounds__(64) turbo_encode_kernel(TurboEncArgs a) {
 // writes e1[k] over it, decoder 2 reads e1[pi(i)] and writes e2[i] over it as la1[pi(i)].  A tile's values are read (by the tile
 // load) before the tile's steps overwrite them and pi is a permutation, so one array serves both.  The last half-iteration writes
 // post in place of the extrinsic value, which leaves llr[k] in natural order for the output pass.
-__device__ __forceinline__ float turbo_finite_or_zero(float v) {
-    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
-}
-__device__ __forceinline__ float turbo_bperm(int byte_addr, float v) {
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
-}
-__device__ __forceinline__ float turbo_group_max(float v) {
-    v = fmaxf(v, __shfl_xor(v, 1, 64));
-    v = fmaxf(v, __shfl_xor(v, 2, 64));
-    return fmaxf(v, __shfl_xor(v, 4, 64));
-}
-
-constexpr int TURBO_ROW = TURBO_CKPT + 1;                    // padded row of the per-group tile arrays
-
+//
+// The half-iteration itself -- lane constants, tile load, forward tile, tail, backward tile -- is turbo_half_iteration of
+// turbo_siso.hpp, which turbo_decode_es_kernel (turbo_es.hip) instantiates too.
 __global__ void __launch_bounds__(64) turbo_decode_kernel(TurboDecArgs a) {
     __shared__ float sm_a[TURBO_CKPT * 64];                  // [step of the tile][lane] forward metrics
     __shared__ float2 sm_x[8 * TURBO_ROW];                   // [group][step] {x, lp}
     __shared__ int sm_i[8 * TURBO_ROW];                      // [group][step] index of the step's output in the block's K floats
     const int lane = int(threadIdx.x), grp = lane >> 3, st = lane & 7;
     const int K = a.q.K;
-    const unsigned uK = unsigned(K);
     const int64_t blk = int64_t(blockIdx.x) * TURBO_GROUP + grp;
     const bool active = blk < a.n_blocks;
     const int64_t seg = active ? blk / a.blocks_per_seg : 0;
@@ -180,113 +170,13 @@ __global__ void __launch_bounds__(64) turbo_decode_kernel(TurboDecArgs a) {
     float2* my_x = sm_x + grp * TURBO_ROW;
     int* my_i = sm_i + grp * TURBO_ROW;
 
-    // forward, lane = s': its predecessors are p0 = 2 (s' & 3) (r3 = 0) and p0 + 1 (r3 = 1); with a = s' >> 2, r1 = (s' >> 1) & 1,
-    // r2 = s' & 1 the p0 branch carries u = a ^ r2, z = a ^ r1, and the other branch has both flipped: its gamma is exactly -gamma.
-    const int f_a = st >> 2, f_r1 = (st >> 1) & 1, f_r2 = st & 1;
-    const float f_su = (f_a ^ f_r2) ? -1.f : 1.f, f_sz = (f_a ^ f_r1) ? -1.f : 1.f;
-    const int addr_s0 = (grp << 3) << 2;
-    const int addr_p0 = addr_s0 + ((2 * (st & 3)) << 2), addr_p1 = addr_p0 + 4;
-    // backward, lane = s = 4 r1 + 2 r2 + r3: input 0 gives a = r2 ^ r3, z = r1 ^ r2 and next = 4 a + (s >> 1); input 1 flips a and z
-    const int b_r1 = st >> 2, b_r2 = (st >> 1) & 1, b_r3 = st & 1;
-    const float b_sz = (b_r1 ^ b_r2) ? -1.f : 1.f;
-    const int n0 = ((b_r2 ^ b_r3) << 2) | (st >> 1);
-    const int addr_n0 = addr_s0 + (n0 << 2), addr_n1 = addr_s0 + ((n0 ^ 4) << 2);
-    // tail, lane = s: the terminating path s, s >> 1, s >> 2 with the signs of (r2 ^ r3, r1 ^ r3) at each of its states
-    const float t_s0 = (b_r2 ^ b_r3) ? -1.f : 1.f, t_s1 = (b_r1 ^ b_r3) ? -1.f : 1.f;
-    const float t_s2 = (b_r1 ^ b_r2) ? -1.f : 1.f, t_s3 = b_r2 ? -1.f : 1.f;
-    const float t_s4 = b_r1 ? -1.f : 1.f;
+    const TurboLane c = turbo_lane(grp, st);
 
     for (int it = 0; it < a.n_iter; ++it) {
         for (int half = 0; half < 2; ++half) {
             const bool first = it == 0 && half == 0;         // la1 = 0
             const bool last = it == a.n_iter - 1 && half == 1;
-
-            // lane st of a group loads steps k0 + st, k0 + st + 8, ..: pi steps by 8 with pi(i + 8) - pi(i) = 8 f1 + f2 (16 i + 64)
-            auto load_tile = [&](int k0, int n) {
-                __syncthreads();
-                unsigned i = unsigned(k0 + st);
-                unsigned p = 0u, g = 0u;
-                if (half) {
-                    p = turbo_qpp_at(a.q, i);
-                    g = (unsigned(a.q.c8) + (unsigned(a.q.c16) * i) % uK) % uK;
-                }
-                for (int j = st; j < n; j += 8, i += 8) {
-                    float x = 0.f, lp = 0.f;
-                    const unsigned idx = half ? p : i;
-                    if (active) {
-                        const float la = first ? 0.f : ext[idx];
-                        x = turbo_finite_or_zero(llr[3 * idx]) + la;
-                        lp = turbo_finite_or_zero(llr[3 * i + 1 + half]);
-                    }
-                    my_x[j] = make_float2(x, lp);
-                    my_i[j] = int(idx);
-                    p = turbo_mod_add(p, g, uK);
-                    g = turbo_mod_add(g, unsigned(a.q.c128), uK);
-                }
-                __syncthreads();
-            };
-            // A_k -> A_{k+n} over the loaded tile; n is a multiple of 8 and so is the tile's first step
-            auto forward_tile = [&](float A, int n, bool keep) -> float {
-                for (int j8 = 0; j8 < n; j8 += 8) {
-#pragma unroll
-                    for (int v = 0; v < 8; ++v) {
-                        const float2 xl = my_x[j8 + v];
-                        if (keep) sm_a[((j8 + v) << 6) + lane] = A;
-                        const float gm = __builtin_fmaf(f_sz, xl.y, f_su * xl.x);
-                        const float c0 = turbo_bperm(addr_p0, A) + gm;
-                        const float c1 = turbo_bperm(addr_p1, A) - gm;
-                        A = fmaxf(c0, c1);
-                        if (v == 7) A = A - turbo_bperm(addr_s0, A);
-                    }
-                }
-                return A;
-            };
-
-            float A = st == 0 ? 0.f : -INFINITY;
-            for (int t = 0; t < n_tiles; ++t) {
-                const int k0 = t * TURBO_CKPT, n = std::min(TURBO_CKPT, K - k0);
-                load_tile(k0, n);
-                ckpt[int64_t(t) << 6] = A;
-                A = forward_tile(A, n, false);
-            }
-
-            float B;
-            {
-                float t[6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) t[j] = active ? turbo_finite_or_zero(llr[3 * K + 6 * half + j]) : 0.f;
-                const float g0 = __builtin_fmaf(t_s1, t[1], t_s0 * t[0]);
-                const float g1 = __builtin_fmaf(t_s3, t[3], t_s2 * t[2]);
-                const float g2 = __builtin_fmaf(t_s4, t[5], t_s4 * t[4]);
-                const float bs = (g0 + g1) + g2;
-                B = bs - turbo_bperm(addr_s0, bs);
-            }
-
-            for (int t = n_tiles - 1; t >= 0; --t) {
-                const int k0 = t * TURBO_CKPT, n = std::min(TURBO_CKPT, K - k0);
-                load_tile(k0, n);
-                forward_tile(ckpt[int64_t(t) << 6], n, true);
-                for (int j8 = n - 8; j8 >= 0; j8 -= 8) {
-                    float mine = 0.f;
-#pragma unroll
-                    for (int v = 7; v >= 0; --v) {
-                        const float2 xl = my_x[j8 + v];
-                        const float Ak = sm_a[((j8 + v) << 6) + lane];
-                        const float gm = __builtin_fmaf(b_sz, xl.y, xl.x);           // gamma of input 0; input 1 has -gamma
-                        const float b0 = turbo_bperm(addr_n0, B), b1 = turbo_bperm(addr_n1, B);
-                        const float m0 = turbo_group_max((Ak + gm) + b0);
-                        const float m1 = turbo_group_max((Ak - gm) + b1);
-                        const float post = 0.5f * (m0 - m1);
-                        const float e = 0.75f * (post - xl.x);
-                        if (v == st) mine = last ? post : e;
-                        float nb = fmaxf(gm + b0, b1 - gm);
-                        if (v == 0) nb = nb - turbo_bperm(addr_s0, nb);
-                        B = nb;
-                    }
-                    if (active) ext[my_i[j8 + st]] = mine;
-                }
-            }
-            __syncthreads();                                 // the half-iteration's stores, before the next one's loads
+            turbo_half_iteration<false>(a.q, llr, ext, nullptr, ckpt, active, active, half, first, last, c, sm_a, my_x, my_i, lane, st);
         }
     }
 

@@ -98,6 +98,12 @@ class TurboOut(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("llr", C.c_void_p)]
 
 
+class TurboEsOut(C.Structure):
+    """ofdm_turbo_es_out: device pointers of the turbo decoder with early termination (None = not wanted)."""
+    _fields_ = [("bits", C.c_void_p), ("bits_mode", C.c_int32), ("llr", C.c_void_p), ("iters", C.c_void_p), ("crc_ok", C.c_void_p),
+                ("stat_stride", C.c_int64)]
+
+
 class TbGroup(C.Structure):
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("K", C.c_int32), ("E", C.c_int32), ("cw_bit_offset", C.c_int64),
                 ("soft_offset", C.c_int64)]
@@ -114,6 +120,11 @@ class TbOut(C.Structure):
     """ofdm_tb_out: device pointers of the transport-block decoder (None = not wanted)."""
     _fields_ = [("payload", C.c_void_p), ("payload_mode", C.c_int32), ("tb_ok", C.c_void_p), ("cb_ok", C.c_void_p),
                 ("syndrome", C.c_void_p)]
+
+
+class TbEsOut(C.Structure):
+    """ofdm_tb_es_out: ofdm_tb_out and the iterations every code block ran."""
+    _fields_ = TbOut._fields_ + [("cb_iters", C.c_void_p)]
 
 
 class TrkCfg(C.Structure):
@@ -194,6 +205,9 @@ PROTOTYPES = {
     "ofdm_rx_reserve_turbo": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "ofdm_turbo_decode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_int32, C.POINTER(TurboOut), C.c_void_p]),
+    "ofdm_rx_reserve_turbo_es": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
+    "ofdm_turbo_decode_es_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TurboEsOut), C.c_void_p]),
     "ofdm_turbo_rm_blocks": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "ofdm_turbo_rm_info": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ofdm_tx_turbo_encode_rm_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
@@ -214,6 +228,10 @@ PROTOTYPES = {
                                         C.c_int32, C.c_void_p, C.c_int64, C.POINTER(TbOut), C.c_void_p]),
     "ofdm_tx_reserve_tb": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32]),
     "ofdm_rx_reserve_tb": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    "ofdm_tb_decode_es_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                           C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(TbEsOut), C.c_void_p]),
+    "ofdm_rx_reserve_tb_es": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "ofdm_fo_create": (C.c_int, [C.POINTER(FoCfg), C.POINTER(C.c_void_p)]),
     "ofdm_fo_destroy": (C.c_int, [C.c_void_p]),
     "ofdm_fo_work": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(FoReport)]),

@@ -360,6 +360,24 @@ class RxEngine:
         check(self.lib.ofdm_turbo_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                 int(f1), int(f2), int(n_iter), C.byref(out), ptr(stream)))
 
+    def reserve_turbo_es(self, n_blocks: int, K: int):
+        """reserve_turbo for turbo_decode_es_frames (a second K-float array per block)."""
+        check(self.lib.ofdm_rx_reserve_turbo_es(self._h, int(n_blocks), int(K)))
+
+    def turbo_decode_es_frames(self, d_llr, n_seg, seg_stride, blocks_per_seg, K, f1, f2, crc_kind, min_iter, max_iter, d_bits=None,
+                               bits_mode=BITS_UNPACKED, d_llr_out=None, d_iters=None, d_crc_ok=None, stat_stride=0, stream=None):
+        """ofdm_turbo_decode_es_frames: turbo_decode_frames with early termination -- from min_iter on a block stops after the
+        first iteration whose hard decisions are divisible by the generator of crc_kind (all K bits, zero mask), at max_iter
+        otherwise; its bits and llr are those of turbo_decode_frames at that n_iter.  iters / crc_ok: uint8 per block at
+        s*stat_stride + b (0 = blocks_per_seg)."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TurboEsOut(addr(d_bits), int(bits_mode), addr(d_llr_out), addr(d_iters), addr(d_crc_ok), int(stat_stride))
+        check(self.lib.ofdm_turbo_decode_es_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
+                                                   int(f1), int(f2), int(crc_kind), int(min_iter), int(max_iter), C.byref(out),
+                                                   ptr(stream)))
+
     def reserve_turbo_rm(self):
         """Loads the turbo rate-matching kernels (before a graph capture)."""
         check(self.lib.ofdm_rx_reserve_turbo_rm(self._h))
@@ -392,6 +410,24 @@ class RxEngine:
         check(self.lib.ofdm_tb_decode_frames(self._h, ptr(d_llr), int(n_tb), int(llr_stride), int(A), int(Z), int(G), int(q), int(N_IR),
                                              int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]), int(rv), ptr(d_rv),
                                              int(n_iter), int(bool(accumulate)), ptr(d_soft), int(soft_stride), C.byref(out), ptr(stream)))
+
+    def reserve_tb_es(self, n_tb: int, A: int, Z: int = 0):
+        """reserve_tb for tb_decode_es_frames (the larger decoder workspace)."""
+        check(self.lib.ofdm_rx_reserve_tb_es(self._h, int(n_tb), int(A), int(Z)))
+
+    def tb_decode_es_frames(self, d_llr, n_tb, llr_stride, A, G, qpp_plus, d_soft, soft_stride, min_iter, max_iter, qpp_minus=(0, 0),
+                            Z=0, q=1, N_IR=0, rv=0, d_rv=None, accumulate=False, d_payload=None, payload_mode=BITS_UNPACKED,
+                            d_tb_ok=None, d_cb_ok=None, d_syndrome=None, d_cb_iters=None, stream=None):
+        """ofdm_tb_decode_es_frames: tb_decode_frames with every code block stopped at its first passing CRC (CRC24B, or the
+        transport block's CRC24A when C = 1) between min_iter and max_iter; cb_iters [n_tb][C] uint8 = the iterations it ran."""
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        out = _lib.TbEsOut(addr(d_payload), int(payload_mode), addr(d_tb_ok), addr(d_cb_ok), addr(d_syndrome), addr(d_cb_iters))
+        check(self.lib.ofdm_tb_decode_es_frames(self._h, ptr(d_llr), int(n_tb), int(llr_stride), int(A), int(Z), int(G), int(q),
+                                                int(N_IR), int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]),
+                                                int(rv), ptr(d_rv), int(min_iter), int(max_iter), int(bool(accumulate)), ptr(d_soft),
+                                                int(soft_stride), C.byref(out), ptr(stream)))
 
     # ---- Gold-sequence descrambling in front of the decoder, CRC check behind it (TS 36.211 7.2, TS 36.212 5.1.1) ----
     def reserve_bitproc(self):
