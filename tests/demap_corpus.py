@@ -1,7 +1,7 @@
 """Planted de-mapper inputs: symbols whose coordinates sit ON the hard-decision edges of each modulation, one or two ulps
 either side of them, and at the float32 extremes (shared by test_demap_rules.py and test_gpu_fused_demap_edges.py).
 
-The edges are those of the float32 rules in oracle.demap_hard / csrc/rx_demod.hpp:hard_bits:
+The edges are those of the float32 rules in oracle.demap_hard / csrc/demap_hard.hpp:hard_bits:
   BPSK    x > 0
   QPSK    (x < 0) xor (|x| > SQRT2_F32)              (plus the literal tie path for an exactly-zero coordinate)
   16-QAM  x < 0, |x| > float32(2/sqrt(10))

@@ -1,4 +1,4 @@
-// demap_rules.hip -- the fused de-mapper's hard-decision functions (csrc/rx_demod.hpp) run on the device, one output per variant.
+// demap_rules.hip -- the fused de-mapper's hard-decision functions (csrc/demap_hard.hpp) run on the device, one output per variant.
 //
 //   demap_rules MOD in.bin outdir
 //     in.bin   complex64[n], n % 4 == 0 (symbols, in the order the groups of pack4 / pairs of pack2 take them)
@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "rx_demod.hpp"
+#include "demap_hard.hpp"
 
 using ofdm::cf;
 

@@ -1,6 +1,6 @@
 """Every hard-decision path of the de-mappers, input by input, at its decision edges.
 
-The fused de-mapper decides with hand-written v_cmp / v_addc chains (pack4 / pack2 in csrc/rx_demod.hpp) next to the plain
+The fused de-mapper decides with hand-written v_cmp / v_addc chains (pack4 / pack2 in csrc/demap_hard.hpp) next to the plain
 C++ rule hard_bits<MOD>; the standalone de-mapper (ofdm_demap) with hard_bits through word stores.  Random or noisy symbols
 almost never land on a threshold, so the inputs here are planted (tests/demap_corpus.py): thresholds and their neighbours
 at 1 and 2 ulps, +-0, denormals, FLT_MIN / FLT_MAX, values whose four-way product overflows, inf and NaN.
