@@ -25,11 +25,11 @@ namespace ofdm {
 // complex multiply-add per step j and alignment: O(B + cp) per trial instead of two N-point FFTs.
 //
 // The recurrence runs in fp32, so it only SCREENS: a block of B trials starts from an exactly evaluated anchor trial
-// (the same sync_trial as everywhere else); a trial whose screened peak exceeds (1 - 1e-3) * gate * MM -- or whose window
+// (the same sync_trial as everywhere else); a trial whose screened peak exceeds (1 - 2e-4) * gate * MM -- or whose window
 // energy is too small for the sliding sums to be trusted -- is re-evaluated exactly, in order, and only the exact value
-// decides (:166).  Trials the screen rejects lie at least 1e-3 * gate * MM below the gate, two orders of magnitude more
-// than the recurrence can drift over one block (<= 256 steps of ~6e-8 relative rounding), so the accepted trial and its
-// lag are those of the exhaustive search.  Frames whose sync sits at trial 0 never enter the recurrence.
+// decides (:166).  Trials the screen rejects lie at least 2e-4 * gate * MM below the gate, ten times what the recurrence
+// can drift over one block (<= 256 steps of ~6e-8 relative rounding), so the accepted trial and its lag are those of the
+// exhaustive search.  Frames whose sync sits at trial 0 never enter the recurrence.
 // Preconditions checked by the host: S == 1, stride == 1, Ks == N - 2, no rotator, B + cp <= SCAN_QM * T.
 #ifndef OFDM_SCAN_MX_T256
 #define OFDM_SCAN_MX_T256 5
