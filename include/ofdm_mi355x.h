@@ -231,6 +231,76 @@ int64_t ofdm_rx_demod_frames_pilots(ofdm_rx* h, const float* d_iq, int64_t n_fra
                                     int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t mode,
                                     const ofdm_pilot_out* out, const ofdm_soft_out* soft, void* stream);
 
+/* ------------------------------------------------------------------------------------------ channel-state-weighted LLRs
+ * An extension the reference does not have.  ofdm_demap_frames restates BitRecovery: linear distances and ONE sigma per frame.
+ * Behind the one-tap MMSE equaliser the symbol of a bin with channel power a = |H|^2 is shrunk by a/(a + rho), rho = 1/SNR of
+ * the equaliser, and carries noise of variance sigma_n^2/a; the max-log LLR of the unbiased symbol is therefore (a/sigma_n^2)
+ * times a difference of SQUARED distances, and a faded bin weighs little.  This text is the definition; tests/csi_ref.py
+ * restates it in NumPy and the library equals that bit for bit.
+ *
+ * All arithmetic is float32, every product, sum, difference and quotient rounded on its own (no fused multiply-add), division
+ * correctly rounded.  sigma2 is the only double.  Per symbol: z complex64, a = float32 channel power of the symbol's bin,
+ * rho float32, w_den = float(sigma2) of the symbol's segment.
+ *  1. The symbol is USABLE iff a is finite and a > 0; z.re and z.im are finite and not both zero; s = (a + rho)/a is finite;
+ *     u = (z.re*s, z.im*s) is finite.  Zero rows of guard-failed patterns, frames without a sync and bins without an estimate are
+ *     therefore erasures.
+ *  2. Axis levels are the library's float32 ones: +-0.70710678f for QPSK (bit 0 <-> the positive level), else
+ *     l_q = float(2q - (M-1)) * u, q = 0..M-1, M = 4 (u = 0.31622776601683794f) or 8 (u = 0.15430334996209191f), with the TS 36.211
+ *     7.1 labels of ofdm_demap: axis bit 0 = (l < 0); 16-QAM bit 1 = (|2q-(M-1)| == 3); 64-QAM bit 1 = (|.| > 4), bit 2 = (|.| == 1 or 7).
+ *  3. For axis bit j of coordinate x (u.re or u.im):  d = min_{l: bit = 1} (x-l)*(x-l)  -  min_{l: bit = 0} (x-l)*(x-l),
+ *     explicit minima over the levels.
+ *  4. Bit order b0..b(bps-1) per symbol as ofdm_demap: b0 = axis bit 0 of re, b1 = axis bit 0 of im, b2 = axis bit 1 of re, ...
+ *  5. llr = (a / w_den) * d  if the symbol is usable, w_den is finite and > 0, and the product is finite; else llr = +0.0f.
+ *     Positive favours bit 0 (the convention of ofdm_soft_out.llr).  No non-finite value leaves the call.
+ *  6. Noise term of a usable symbol: e = a * (mr + mi), mr / mi = min over ALL levels of (u.re-l)*(u.re-l) / (u.im-l)*(u.im-l)
+ *     (the squared distance to the nearest point).  A symbol whose e is not finite is left out.
+ *  7. OFDM_CSI_NOISE_EST: sigma2 = sum double(e) / n_used per segment, n_used (int64) = the symbols of step 6 that are in the
+ *     sum; n_used == 0 gives sigma2 = 0 and every LLR +0.  The order of the sum is fixed by (rows, row_len) alone: one partial
+ *     per (segment, slice of 2048 symbols), the partials added in a fixed order, no atomics -- a segment's outputs are the same
+ *     bits alone, in any batch, at any alignment and on every call.
+ *     OFDM_CSI_NOISE_GIVEN: sigma2 = noise_var for every segment and no estimation pass runs; the sigma2 output, if wanted, is
+ *     that value and n_used the number of usable symbols (step 1) of the segment.
+ * The estimate of step 7 is decision-directed: at low SNR the nearest point is often the wrong one and sigma2 comes out too
+ * SMALL.  Inside one code block that is harmless (max-log decoders are invariant to a common scale of their LLRs); it matters
+ * where LLRs of different frames are added (HARQ combining) -- pass a known noise_var there. */
+typedef enum { OFDM_CSI_NOISE_EST = 0, OFDM_CSI_NOISE_GIVEN = 1 } ofdm_csi_noise_mode;
+typedef enum { OFDM_CSI_ROWS_ALL = 0, OFDM_CSI_ROWS_DATA = 1 } ofdm_csi_layout;
+typedef struct ofdm_csi_out {     /* DEVICE pointers; NULL = not wanted */
+    float*   llr;      /* [n_seg][rows*row_len*bps] float32, dense */
+    double*  sigma2;   /* [n_seg] the noise variance the segment's LLRs were scaled with */
+    int64_t* n_used;   /* [n_seg] */
+} ofdm_csi_out;
+/* Device workspace (partials and the per-(segment, entry) tables) for n_seg segments of `rows` rows of row_len symbols: grows,
+ * never shrinks; synchronises the device.  Call it before capturing the calls below into a hipGraph; inside a capture a call
+ * that needs more is refused. */
+int ofdm_rx_reserve_csi(ofdm_rx* h, int64_t n_seg, int64_t rows, int64_t row_len);
+/* d_csi[f*csi_stride + j] = re*re + im*im (float32, each product rounded) of the channel estimate of frame f of the LAST
+ * ofdm_rx_demod_frames call on this handle (the est_chan_freq_P row ofdm_rx_get_frame_state returns), in bin-list order:
+ * OFDM_CSI_ROWS_ALL: j over binsP(num_data_bins); OFDM_CSI_ROWS_DATA: the Kd' non-pilot entries in list order (needs
+ * ofdm_rx_set_pilots, else OFDM_ERR_INVALID).  n_frames beyond that call's count: OFDM_ERR_INVALID.  Asynchronous on `stream`
+ * (NULL = the handle's stream), one launch. */
+int ofdm_rx_csi_frames(ofdm_rx* h, int64_t n_frames, int32_t layout, float* d_csi, int64_t csi_stride, void* stream);
+/* The stage on any device buffer: segment s = `rows` rows of row_len complex64 symbols at d_sym + s*seg_stride (complex items);
+ * entry j of every row of segment s has a = d_csi[s*csi_stride + j].  modulation 2, 4 or 6 (BPSK: OFDM_ERR_INVALID).
+ * Asynchronous on `stream`: up to four launches, no host synchronisation and no allocation once ofdm_rx_reserve_csi covers
+ * the call.  n_seg == 0, rows == 0, row_len == 0 or an `out` without any pointer is a no-op returning OFDM_OK.  Argument
+ * errors return OFDM_ERR_INVALID with the reason in ofdm_last_error() before the handle is read: negative counts, seg_stride <
+ * rows*row_len, csi_stride < row_len, unknown noise_mode, OFDM_CSI_NOISE_GIVEN with noise_var not finite or <= 0, rho negative
+ * or not finite, index range exceeded (n_seg > 2^31, row_len > 2^30, rows*row_len, n_seg*seg_stride or n_seg*csi_stride > 2^40).
+ * d_sym, d_csi and the outputs must not overlap. */
+int ofdm_demap_csi_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride,
+                          const float* d_csi, int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode,
+                          double noise_var, const ofdm_csi_out* out, void* stream);
+/* ofdm_rx_demod_frames with the same arguments (same d_eq / d_bits / d_tsr bits, same return value n_dsym), then
+ * ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL) into the workspace and ofdm_demap_csi_frames over d_eq with one segment per frame:
+ * rows = n_dsym, row_len = num_data_bins, rho = 1/snr_data of the handle's equaliser, modulation = cfg.modulation.  Needs d_eq.
+ * out == NULL or without any pointer: exactly ofdm_rx_demod_frames.
+ * Signals with pilots: chain ofdm_rx_demod_frames_pilots -> ofdm_rx_csi_frames(OFDM_CSI_ROWS_DATA) -> ofdm_demap_csi_frames over
+ * its out->data (rows = n_dsym, row_len = Kd', rho = 1/snr as above); the tracking stage only rotates, so a is unchanged. */
+int64_t ofdm_rx_demod_frames_csi(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                 float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr, int32_t noise_mode,
+                                 double noise_var, const ofdm_csi_out* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

@@ -94,6 +94,14 @@ struct ofdm_rx {
     float p_kbar = 0.f, p_inv_skk = 0.f;
     cf* f_usum = nullptr;                // [n_seg][rows] pilot sums of ofdm_pilot_track_frames (read by the cfo launch)
     int64_t cap_usum = 0;
+    // ---- channel-state-weighted LLRs (ofdm_rx_reserve_csi)
+    int64_t last_frames = 0;             // frames of the last ofdm_rx_demod_frames call: the rows of f_H ofdm_rx_csi_frames may read
+    double* c_part_e = nullptr;          // [n_seg][seg_slices(rows*row_len)] noise partials
+    long long* c_part_n = nullptr;       //                                   their usable counts
+    int64_t cap_csi_items = 0;
+    float2* c_tab = nullptr;             // [n_seg][row_len] {s_j, w_j}
+    float* c_a = nullptr;                // [n_seg][row_len] |H|^2 rows of ofdm_rx_demod_frames_csi
+    int64_t cap_csi_tab = 0;
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;

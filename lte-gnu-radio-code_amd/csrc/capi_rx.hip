@@ -16,7 +16,8 @@ int ofdm_rx_destroy(ofdm_rx* h) {
     if (h->pin_out) (void)hipHostFree(h->pin_out);
     free_dev(&h->tb_ws, &h->d_pack, &h->d_tw, &h->d_zc, &h->d_in, &h->d_edf, &h->s_tsr, &h->s_H, &h->s_htime, &h->s_esf, &h->s_eqg, &h->s_gain,
              &h->s_ysc, &h->d_trial_m, &h->d_trial_d, &h->d_partial, &h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime, &h->d_scan_g,
-             &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws);
+             &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws, &h->c_part_e,
+             &h->c_part_n, &h->c_tab, &h->c_a);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -165,6 +166,7 @@ int ofdm_rx_reserve(ofdm_rx* h, int64_t n_frames) {
     HIP_TRY(hipDeviceSynchronize());
     free_dev(&h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime);
     h->cap_frames = 0;
+    h->last_frames = 0;
     int rc = dev_alloc(&h->f_tsr, size_t(n_frames) * 4);
     if (rc == OFDM_OK) rc = dev_alloc(&h->f_H, size_t(n_frames) * h->dev.nfft);
     if (rc == OFDM_OK) rc = dev_alloc(&h->f_gain, size_t(n_frames) * h->dev.Kd);
@@ -216,6 +218,7 @@ int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, in
     hipEvent_t* pev = h->ev + 3 * (h->prof_calls % ofdm_rx::PROF_RING);
     if (h->profiling) HIP_TRY(hipEventRecord(pev[0], s));
     HIP_TRY(launch_rx_sync(d, sa, s));
+    h->last_frames = n_frames;           // rows of f_H this call wrote (ofdm_rx_csi_frames)
     if (h->profiling) HIP_TRY(hipEventRecord(pev[1], s));
 
     if (n_dsym > 0 && (d_eq || d_bits)) {

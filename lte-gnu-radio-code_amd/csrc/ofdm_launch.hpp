@@ -130,6 +130,33 @@ struct SegDemapArgs {
     double* partial;         // [n_seg][n_slices] workspace
 };
 
+// ---- channel-state-weighted LLRs (ofdm_demap_csi_frames): segment s = rows rows of row_len symbols at sym + s*seg_stride; entry j
+// of every row of segment s has the channel power csi[s*csi_stride + j].  The two divides of the contract depend on (segment, entry)
+// only and live in tab[s][j] = {s_j, w_j}; the noise sum is cut into the slices of the soft de-mapper above (SEG_SLICE symbols).
+struct CsiArgs {
+    const cf* sym;
+    int64_t n_seg, rows, seg_stride;      // complex items
+    int row_len;
+    int64_t seg_len;         // rows * row_len
+    int64_t n_slices;        // seg_slices(seg_len)
+    const float* csi;        // [n_seg][csi_stride] |H|^2 per entry
+    int64_t csi_stride;
+    float rho;               // 1 / SNR of the equaliser
+    int mod;                 // 2, 4, 6
+    int est;                 // OFDM_CSI_NOISE_EST (1) / OFDM_CSI_NOISE_GIVEN (0)
+    double noise_var;        // GIVEN: sigma^2 of every segment
+    float* llr;              // [n_seg][seg_len*mod], or null
+    double* sigma2;          // [n_seg], or null
+    long long* n_used;       // [n_seg], or null
+    float2* tab;             // [n_seg][row_len] workspace {s_j (0: entry is an erasure), a_j until the noise is known, then w_j}
+    double* part_e;          // [n_seg][n_slices] workspace
+    long long* part_n;       // [n_seg][n_slices] workspace
+};
+hipError_t launch_demap_csi(const CsiArgs& a, hipStream_t s);
+// a[f][j] = |H[f][bin]|^2 of the j-th entry of binsP(K) (src == null) or of its src[j]-th entry (the non-pilot entries)
+hipError_t launch_csi_frames(const cf* H, int nfft, int K, const uint16_t* src, int n_out, int64_t n_frames, float* out,
+                             int64_t out_stride, hipStream_t s);
+
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
 // consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.

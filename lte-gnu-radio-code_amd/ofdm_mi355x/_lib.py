@@ -24,6 +24,8 @@ COMPAT_RXOFDM = 1
 BITS_NONE, BITS_PACKED, BITS_UNPACKED = 0, 1, 2
 PILOT_CPE, PILOT_CPE_SLOPE = 0, 1
 CRC24A, CRC24B, CRC16, CRC8 = 0, 1, 2, 3
+CSI_NOISE_EST, CSI_NOISE_GIVEN = 0, 1
+CSI_ROWS_ALL, CSI_ROWS_DATA = 0, 1
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -81,6 +83,11 @@ class PilotOut(C.Structure):
     """ofdm_pilot_out: device pointers of the pilot tracking stage (None = not wanted)."""
     _fields_ = [("data", C.c_void_p), ("bits", C.c_void_p), ("bits_mode", C.c_int32), ("cpe", C.c_void_p), ("slope", C.c_void_p),
                 ("cfo", C.c_void_p)]
+
+
+class CsiOut(C.Structure):
+    """ofdm_csi_out: device pointers of the channel-state-weighted LLR stage (None = not wanted)."""
+    _fields_ = [("llr", C.c_void_p), ("sigma2", C.c_void_p), ("n_used", C.c_void_p)]
 
 
 class TbccOut(C.Structure):
@@ -172,6 +179,12 @@ PROTOTYPES = {
                                           C.POINTER(PilotOut), C.c_void_p]),
     "ofdm_rx_demod_frames_pilots": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                                 C.c_int32, C.POINTER(PilotOut), C.POINTER(SoftOut), C.c_void_p]),
+    "ofdm_rx_reserve_csi": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
+    "ofdm_rx_csi_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ofdm_demap_csi_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_float, C.c_int32, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_csi": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
     "ofdm_tbcc_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
     "ofdm_tx_tbcc_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_int64, C.c_void_p]),

@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import BITS_NONE, BITS_PACKED, BITS_UNPACKED, MODULATION_BITS, PILOT_CPE, check, ptr
+from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, CSI_NOISE_EST, CSI_ROWS_ALL, CSI_ROWS_DATA, MODULATION_BITS, PILOT_CPE,
+                   check, ptr)
 
 
 def bins_p(num_bins: int, nfft: int) -> np.ndarray:
@@ -308,6 +309,52 @@ class RxEngine:
         return int(check(self.lib.ofdm_rx_demod_frames_pilots(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
                                                               int(frame_len), ptr(d_eq), ptr(d_tsr), int(mode), C.byref(out),
                                                               C.byref(soft), ptr(stream))))
+
+    # ---- channel-state-weighted LLRs: every symbol weighed with |H|^2 of its bin (include/ofdm_mi355x.h) ---------------------
+    @staticmethod
+    def _csi_out(d_llr, d_sigma2, d_n_used):
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        return _lib.CsiOut(addr(d_llr), addr(d_sigma2), addr(d_n_used))
+
+    @property
+    def csi_rho(self) -> float:
+        """1/SNR of the handle's data equaliser as the library holds it (float32): the rho of demap_csi_frames behind this
+        receiver (SynchAndChanEst.py:99,245 takes 10^(snr/20); the RXOFDM blocks take snr itself)."""
+        snr = 10.0 ** (self.cfg.snr / 20.0) if self.cfg.compat == _lib.COMPAT_UTSA else self.cfg.snr
+        return float(np.float32(1.0 / snr))
+
+    def reserve_csi(self, n_seg: int, rows: int, row_len: int):
+        """Workspace of csi_frames / demap_csi_frames / demod_frames_csi for n_seg segments of `rows` rows of row_len symbols
+        (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_csi(self._h, int(n_seg), int(rows), int(row_len)))
+
+    def csi_frames(self, n_frames, d_csi, csi_stride=None, layout=CSI_ROWS_ALL, stream=None):
+        """ofdm_rx_csi_frames: d_csi[f][j] = |H|^2 (float32) of frame f of the last demod_frames call, j over bins_p(Kd)
+        (CSI_ROWS_ALL) or over the non-pilot entries (CSI_ROWS_DATA).  csi_stride defaults to the entries per row."""
+        if csi_stride is None:
+            csi_stride = self.cfg.num_data_bins - (getattr(self, "n_pilots", 0) if layout == CSI_ROWS_DATA else 0)
+        check(self.lib.ofdm_rx_csi_frames(self._h, int(n_frames), int(layout), ptr(d_csi), int(csi_stride), ptr(stream)))
+
+    def demap_csi_frames(self, d_sym, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, modulation, d_llr=None,
+                         d_sigma2=None, d_n_used=None, noise_mode=CSI_NOISE_EST, noise_var=0.0, stream=None):
+        """ofdm_demap_csi_frames: segment s = `rows` rows of row_len complex64 symbols at d_sym + s*seg_stride, entry j of every
+        row weighed with d_csi[s*csi_stride + j].  Outputs llr [n_seg][rows*row_len*bps] float32 (positive favours bit 0),
+        sigma2 [n_seg] float64, n_used [n_seg] int64."""
+        out = self._csi_out(d_llr, d_sigma2, d_n_used)
+        check(self.lib.ofdm_demap_csi_frames(self._h, ptr(d_sym), int(n_seg), int(rows), int(row_len), int(seg_stride), ptr(d_csi),
+                                             int(csi_stride), float(rho), _mod_bits(modulation), int(noise_mode), float(noise_var),
+                                             C.byref(out), ptr(stream)))
+
+    def demod_frames_csi(self, d_iq, n_frames, frame_stride, frame_len, d_eq, d_llr=None, d_sigma2=None, d_n_used=None,
+                         noise_mode=CSI_NOISE_EST, noise_var=0.0, d_bits=None, bits_mode=BITS_NONE, d_tsr=None, stream=None) -> int:
+        """demod_frames, then csi_frames(CSI_ROWS_ALL) and demap_csi_frames over d_eq with one segment per frame (n_dsym rows of
+        Kd symbols, the handle's rho and modulation).  Returns n_dsym."""
+        out = self._csi_out(d_llr, d_sigma2, d_n_used)
+        return int(check(self.lib.ofdm_rx_demod_frames_csi(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
+                                                           ptr(d_eq), ptr(d_bits), int(bits_mode), ptr(d_tsr), int(noise_mode),
+                                                           float(noise_var), C.byref(out), ptr(stream))))
 
     # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
     def reserve_tbcc(self, n_blocks: int, K: int):
