@@ -301,6 +301,73 @@ int64_t ofdm_rx_demod_frames_csi(ofdm_rx* h, const float* d_iq, int64_t n_frames
                                  float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr, int32_t noise_mode,
                                  double noise_var, const ofdm_csi_out* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ receive-diversity combining
+ * An extension the reference does not have: maximum-ratio combining (MRC) of B receive branches (antennas) behind the batch
+ * receiver, with max-log LLRs of the combined symbol.  Behind the one-tap MMSE equaliser a branch's symbol z of a bin with channel
+ * power a = |H|^2 is conj(H) y / (a + rho), so z (a + rho) / sigma_b^2 is the matched-filter output over the branch's noise
+ * variance; their sum over the branches divided by A = sum a / sigma_b^2 is the unbiased combined symbol, which carries noise of
+ * variance 1/A.  This text is the definition; tests/mrc_ref.py restates it in NumPy and the library equals that bit for bit.
+ *
+ * All arithmetic is float32, every product, sum, difference and quotient rounded on its own (no fused multiply-add), division
+ * correctly rounded.  The noise variances are the only doubles.  Layout, branch-major: branch b of segment s is the unit
+ * g = b*n_seg + s: `rows` rows of row_len complex64 symbols at d_sym + g*seg_stride (complex items), channel powers at
+ * d_csi + g*csi_stride, noise variance sigma2[g] with w_den = float(sigma2[g]).
+ *  1. Per (unit g, entry j), a = d_csi[g*csi_stride + j], rho the float32 equaliser term: c = (a + rho)/w_den, t = a/w_den.
+ *     The entry is USABLE iff a is finite and > 0; w_den is finite and > 0; c is finite; t is finite and > 0.
+ *  2. Per symbol and branch, z the equalised symbol: p = (z.re*c, z.im*c).  The branch TAKES PART iff its entry is usable;
+ *     z.re and z.im are finite and not both zero; p is finite.
+ *  3. Over the branches that take part, in the order b = 0, 1, ..., B-1 and starting from +0.0f:  N = sum p (re and im
+ *     separately), A = sum t.  A branch that does not take part leaves the sums as they are.
+ *  4. u = (N.re/A, N.im/A).  The symbol is USABLE iff at least one branch took part, A is finite and > 0, and u is finite.
+ *  5. d per axis bit of u exactly as steps 2-4 of the channel-state-weighted LLR contract above: the same float32 levels and
+ *     labels, explicit minima of squared differences, the bit order of ofdm_demap.
+ *  6. llr = A * d if the symbol is usable and the product is finite, else +0.0f.  Positive favours bit 0.  No non-finite value
+ *     leaves the call.
+ *  7. sym = u if the symbol is usable, else 0+0j; weight = A if usable, else +0.0f.
+ * A branch without a sync, the zero rows of a guard-failed pattern, a bin without an estimate and a branch whose sigma2 is 0 are
+ * therefore erasures of that branch alone: the others carry the symbol.  The result depends on (B, rows, row_len) and the data
+ * alone: the same bits in any batch, at either alignment and on every call.
+ * Noise: OFDM_MRC_NOISE_GIVEN takes the HOST array h_noise_var[n_branch] (each finite and > 0, else OFDM_ERR_INVALID), read at
+ * call time and passed as kernel arguments -- a captured graph keeps them; sigma2[g] = h_noise_var[b].  OFDM_MRC_NOISE_SEG takes
+ * the DEVICE array d_sigma2[n_branch*n_seg] indexed by g: the layout ofdm_csi_out.sigma2 has when the channel-state-weighted
+ * LLR stage runs over the B*n_seg units as its segments.  OFDM_MRC_NOISE_EST (ofdm_rx_demod_frames_mrc only) estimates them.
+ * Estimates are decision-directed and come out too small at low SNR (see above); a branch whose estimate is too small by a
+ * larger factor than the others' is weighed too heavily -- pass known variances where they are known. */
+#define OFDM_MRC_MAX_BRANCHES 8
+typedef enum { OFDM_MRC_NOISE_GIVEN = 0, OFDM_MRC_NOISE_SEG = 1, OFDM_MRC_NOISE_EST = 2 } ofdm_mrc_noise_mode;
+typedef struct ofdm_mrc_out {   /* DEVICE pointers; NULL = not wanted */
+    float* llr;      /* [n_seg][rows*row_len*bps] */
+    float* sym;      /* [n_seg][rows*row_len] complex64 */
+    float* weight;   /* [n_seg][rows*row_len] */
+} ofdm_mrc_out;
+/* Device workspace of the two calls below for n_branch branches of n_seg segments of `rows` rows of row_len symbols (it
+ * includes ofdm_rx_reserve_csi over the n_branch*n_seg units): grows, never shrinks; synchronises the device.  Call it before
+ * capturing the calls below into a hipGraph; inside a capture a call that needs more is refused. */
+int ofdm_rx_reserve_mrc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len);
+/* The stage on any device buffer.  modulation 2, 4 or 6; noise_mode OFDM_MRC_NOISE_GIVEN or OFDM_MRC_NOISE_SEG
+ * (OFDM_MRC_NOISE_EST: OFDM_ERR_INVALID).  Asynchronous on `stream`: two launches, no host synchronisation and no allocation
+ * once ofdm_rx_reserve_mrc covers the call.  n_seg == 0, rows == 0, row_len == 0 or an `out` without any pointer is a no-op
+ * returning OFDM_OK.  Argument errors return OFDM_ERR_INVALID with the reason in ofdm_last_error() before the handle is read:
+ * negative counts, n_branch outside 1..8, seg_stride < rows*row_len, csi_stride < row_len, unknown noise_mode, the pointer the
+ * mode needs missing, a given variance not finite or <= 0, rho negative or not finite, index range exceeded (n_branch*n_seg >
+ * 2^31, row_len > 2^30, rows*row_len, n_branch*n_seg*seg_stride or n_branch*n_seg*csi_stride > 2^40).  d_sym, d_csi, d_sigma2
+ * and the outputs must not overlap. */
+int ofdm_combine_csi_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len,
+                            int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, int32_t modulation,
+                            int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
+                            const ofdm_mrc_out* out, void* stream);
+/* d_iq holds n_branch*n_frames frames at one frame_stride, frame f of branch b at index b*n_frames + f.  Runs
+ * ofdm_rx_demod_frames over all of them (d_eq is required, gets the bits of that call and is left for the caller; d_tsr is
+ * [n_branch*n_frames][4]), ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL) into the workspace, for OFDM_MRC_NOISE_EST the estimation pass
+ * of ofdm_demap_csi_frames over the n_branch*n_frames units (sigma2 of a unit is bit for bit what ofdm_rx_demod_frames_csi
+ * reports for that frame), then the combiner with rows = n_dsym, row_len = num_data_bins, rho = 1/snr_data of the handle's
+ * equaliser and modulation = cfg.modulation.  noise_mode OFDM_MRC_NOISE_GIVEN (h_noise_var[n_branch]) or OFDM_MRC_NOISE_EST.
+ * d_sigma2_out [n_branch*n_frames] (may be NULL) receives the variances used.  out == NULL or without any pointer, and no
+ * d_sigma2_out: exactly ofdm_rx_demod_frames.  Returns n_dsym or a negative status. */
+int64_t ofdm_rx_demod_frames_mrc(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames, int64_t frame_stride,
+                                 int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
+                                 const double* h_noise_var, const ofdm_mrc_out* out, double* d_sigma2_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

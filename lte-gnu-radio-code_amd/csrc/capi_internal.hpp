@@ -102,6 +102,11 @@ struct ofdm_rx {
     float2* c_tab = nullptr;             // [n_seg][row_len] {s_j, w_j}
     float* c_a = nullptr;                // [n_seg][row_len] |H|^2 rows of ofdm_rx_demod_frames_csi
     int64_t cap_csi_tab = 0;
+    // ---- receive-diversity combining (ofdm_rx_reserve_mrc); the composite call also uses the workspace above
+    float2* m_tab = nullptr;             // [n_branch*n_seg][row_len] {c, t}
+    int64_t cap_mrc_tab = 0;
+    double* m_sigma2 = nullptr;          // [n_branch*n_seg] estimated variances of ofdm_rx_demod_frames_mrc
+    int64_t cap_mrc_units = 0;
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;

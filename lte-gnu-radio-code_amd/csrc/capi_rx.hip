@@ -17,7 +17,7 @@ int ofdm_rx_destroy(ofdm_rx* h) {
     free_dev(&h->tb_ws, &h->d_pack, &h->d_tw, &h->d_zc, &h->d_in, &h->d_edf, &h->s_tsr, &h->s_H, &h->s_htime, &h->s_esf, &h->s_eqg, &h->s_gain,
              &h->s_ysc, &h->d_trial_m, &h->d_trial_d, &h->d_partial, &h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime, &h->d_scan_g,
              &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws, &h->c_part_e,
-             &h->c_part_n, &h->c_tab, &h->c_a);
+             &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);

@@ -157,6 +157,31 @@ hipError_t launch_demap_csi(const CsiArgs& a, hipStream_t s);
 hipError_t launch_csi_frames(const cf* H, int nfft, int K, const uint16_t* src, int n_out, int64_t n_frames, float* out,
                              int64_t out_stride, hipStream_t s);
 
+// ---- receive-diversity combining (ofdm_combine_csi_frames): unit g = b*n_seg + s is branch b of output segment s, rows rows of
+// row_len symbols at sym + g*seg_stride with the channel powers csi[g*csi_stride + j].  tab[g][j] = {c, t} holds the divisions that
+// depend on (unit, entry) alone; the work is cut into the slices of the soft de-mapper above (SEG_SLICE output symbols).
+constexpr int MRC_MAX_BRANCHES = 8;
+struct MrcArgs {
+    const cf* sym;
+    int n_branch;
+    int64_t n_seg, rows, seg_stride;      // complex items
+    int row_len;
+    int64_t seg_len;         // rows * row_len
+    int64_t n_slices;        // seg_slices(seg_len)
+    const float* csi;        // [n_branch*n_seg][csi_stride] |H|^2 per entry
+    int64_t csi_stride;
+    float rho;               // 1 / SNR of the equaliser
+    int mod;                 // 2, 4, 6
+    double noise_var[MRC_MAX_BRANCHES];   // sigma2 == null: sigma^2 of every unit of branch b
+    const double* sigma2;    // [n_branch*n_seg] per unit, or null
+    float* llr;              // [n_seg][seg_len*mod], or null
+    cf* osym;                // [n_seg][seg_len], or null
+    float* weight;           // [n_seg][seg_len], or null
+    double* sigma2_out;      // [n_branch*n_seg] the variances used, or null
+    float2* tab;             // [n_branch*n_seg][row_len] workspace
+};
+hipError_t launch_combine_mrc(const MrcArgs& a, hipStream_t s);
+
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
 // consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.

@@ -1,6 +1,7 @@
 """MI355X-native OFDM PHY hot path: Python host side of libofdm_mi355x.so."""
 from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, COMPAT_RXOFDM, COMPAT_UTSA, CRC8, CRC16, CRC24A, CRC24B,  # noqa: F401
-                   CSI_NOISE_EST, CSI_NOISE_GIVEN, CSI_ROWS_ALL, CSI_ROWS_DATA, LIB_PATH, OfdmError, OfdmLibraryError, PILOT_CPE,
+                   CSI_NOISE_EST, CSI_NOISE_GIVEN, CSI_ROWS_ALL, CSI_ROWS_DATA, LIB_PATH, MRC_NOISE_EST, MRC_NOISE_GIVEN,
+                   MRC_NOISE_SEG, OfdmError, OfdmLibraryError, PILOT_CPE,
                    PILOT_CPE_SLOPE, load)
 from .engine import (DeviceBuffer, FoEngine, RxEngine, TrkEngine, TxEngine, bins_p, count_bit_errors, crc_bits,  # noqa: F401
                      crc_compute, crc_compute_long, gold_bits, tb_geometry, tbcc_blocks, tbcc_rm_blocks, turbo_blocks,

@@ -26,6 +26,8 @@ PILOT_CPE, PILOT_CPE_SLOPE = 0, 1
 CRC24A, CRC24B, CRC16, CRC8 = 0, 1, 2, 3
 CSI_NOISE_EST, CSI_NOISE_GIVEN = 0, 1
 CSI_ROWS_ALL, CSI_ROWS_DATA = 0, 1
+MRC_NOISE_GIVEN, MRC_NOISE_SEG, MRC_NOISE_EST = 0, 1, 2
+MRC_MAX_BRANCHES = 8
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -88,6 +90,11 @@ class PilotOut(C.Structure):
 class CsiOut(C.Structure):
     """ofdm_csi_out: device pointers of the channel-state-weighted LLR stage (None = not wanted)."""
     _fields_ = [("llr", C.c_void_p), ("sigma2", C.c_void_p), ("n_used", C.c_void_p)]
+
+
+class MrcOut(C.Structure):
+    """ofdm_mrc_out: device pointers of the receive-diversity combiner (None = not wanted)."""
+    _fields_ = [("llr", C.c_void_p), ("sym", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class TbccOut(C.Structure):
@@ -185,6 +192,13 @@ PROTOTYPES = {
                                         C.c_float, C.c_int32, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
     "ofdm_rx_demod_frames_csi": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
+    "ofdm_rx_reserve_mrc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
+    "ofdm_combine_csi_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_int64, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                          C.POINTER(MrcOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_mrc": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(MrcOut), C.c_void_p,
+                                             C.c_void_p]),
     "ofdm_tbcc_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
     "ofdm_tx_tbcc_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_int64, C.c_void_p]),

@@ -10,8 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, CSI_NOISE_EST, CSI_ROWS_ALL, CSI_ROWS_DATA, MODULATION_BITS, PILOT_CPE,
-                   check, ptr)
+from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, CSI_NOISE_EST, CSI_ROWS_ALL, CSI_ROWS_DATA, MODULATION_BITS, MRC_NOISE_EST,
+                   MRC_NOISE_GIVEN, MRC_NOISE_SEG, PILOT_CPE, check, ptr)
 
 
 def bins_p(num_bins: int, nfft: int) -> np.ndarray:
@@ -355,6 +355,57 @@ class RxEngine:
         return int(check(self.lib.ofdm_rx_demod_frames_csi(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
                                                            ptr(d_eq), ptr(d_bits), int(bits_mode), ptr(d_tsr), int(noise_mode),
                                                            float(noise_var), C.byref(out), ptr(stream))))
+
+    # ---- receive-diversity combining: B branches added with maximum-ratio weights, LLRs of the sum (include/ofdm_mi355x.h) ------
+    @staticmethod
+    def _mrc_out(d_llr, d_sym_out, d_weight):
+        def addr(x):
+            p = ptr(x)
+            return None if p is None else p.value
+        return _lib.MrcOut(addr(d_llr), addr(d_sym_out), addr(d_weight))
+
+    @staticmethod
+    def _mrc_noise(noise_var, n_branch):
+        """the host array of OFDM_MRC_NOISE_GIVEN: n_branch doubles"""
+        nv = [float(v) for v in noise_var]
+        if len(nv) != int(n_branch):
+            raise ValueError("noise_var must hold n_branch = %d numbers, got %d" % (int(n_branch), len(nv)))
+        return (C.c_double * len(nv))(*nv)
+
+    def reserve_mrc(self, n_branch: int, n_seg: int, rows: int, row_len: int):
+        """Workspace of combine_csi_frames / demod_frames_mrc for n_branch branches of n_seg segments of `rows` rows of row_len
+        symbols (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_mrc(self._h, int(n_branch), int(n_seg), int(rows), int(row_len)))
+
+    def combine_csi_frames(self, d_sym, n_branch, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, modulation,
+                           noise_var=None, d_sigma2=None, d_llr=None, d_sym_out=None, d_weight=None, stream=None):
+        """ofdm_combine_csi_frames: branch b of segment s is the unit g = b*n_seg + s, `rows` rows of row_len complex64 symbols at
+        d_sym + g*seg_stride with the channel powers d_csi[g*csi_stride + j].  Exactly one of noise_var (n_branch numbers, one
+        variance per branch) and d_sigma2 (device, [n_branch*n_seg] float64, one per unit) is given.  Outputs per segment: llr
+        [rows*row_len*bps] float32 (positive favours bit 0), sym [rows*row_len] complex64, weight [rows*row_len] float32."""
+        if (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("combine_csi_frames: give exactly one of noise_var and d_sigma2")
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_out(d_llr, d_sym_out, d_weight)
+        check(self.lib.ofdm_combine_csi_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(row_len),
+                                               int(seg_stride), ptr(d_csi), int(csi_stride), float(rho), _mod_bits(modulation),
+                                               MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2), C.byref(out),
+                                               ptr(stream)))
+
+    def demod_frames_mrc(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_llr=None, d_sym_out=None,
+                         d_weight=None, d_sigma2=None, d_tsr=None, stream=None) -> int:
+        """demod_frames over the n_branch*n_frames frames of d_iq (frame f of branch b at index b*n_frames + f), then
+        csi_frames(CSI_ROWS_ALL) and combine_csi_frames over d_eq with one segment per frame (n_dsym rows of Kd symbols, the
+        handle's rho and modulation).  noise_var: n_branch numbers, or None for the per-frame estimate of demod_frames_csi.
+        d_sigma2 [n_branch*n_frames] float64 receives the variances used.  Returns n_dsym."""
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_out(d_llr, d_sym_out, d_weight)
+        return int(check(self.lib.ofdm_rx_demod_frames_mrc(self._h, ptr(d_iq), int(n_branch), int(n_frames), int(frame_stride),
+                                                           int(frame_len), ptr(d_eq), ptr(d_tsr),
+                                                           MRC_NOISE_GIVEN if given else MRC_NOISE_EST, nv, C.byref(out),
+                                                           ptr(d_sigma2), ptr(stream))))
 
     # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
     def reserve_tbcc(self, n_blocks: int, K: int):
