@@ -191,8 +191,10 @@ int64_t ofdm_rx_demod_frames_soft(ofdm_rx* h, const float* d_iq, int64_t n_frame
  * For one row, P = the pilots' list indices in ascending order, d_j = the j-th non-pilot list index:
  *   U    = sum_{p in P} z[p] * conj(pilot_value), ascending p, float32
  *   c    = conj(U)/|U| if |U|^2 is finite and > 0, else 1 (zero rows of guard-failed patterns and of frames without a sync
- *          stay zero)
- *   data[j] = c * z[d_j]                                   cpe[row] = U/|U| (the measured rotation), 0 for a row without usable U
+ *          stay zero).  |U|^2 = ur*ur + ui*ui is evaluated in float32 like U itself: a pilot sum whose square overflows float32
+ *          (|U| above about 1.8e19) or underflows it to 0 (|U| below about 1e-23; a square in the denormal range, |U| up to 1e-19,
+ *          may go either way) is "not usable", as is one with a NaN or an Inf in a pilot entry
+ *   data[j] = c * z[d_j]                                  cpe[row] = U/|U| (the measured rotation), 0 for a row without usable U
  *   bits = the hard decision (ofdm_demap's rules) of the STORED float32 data[j], cfg.modulation 2 / 4 / 6 bits per symbol
  * OFDM_PILOT_CPE_SLOPE also removes a phase that is linear in the bin offset k: theta_p = arg(z[p] conj(pilot_value) c),
  *   tau = sum (k_p - kbar) theta_p / sum (k_p - kbar)^2, delta = mean theta - tau kbar,

@@ -24,18 +24,30 @@ def layout(K, locations):
     return pidx, offs[pidx], didx, offs[didx]
 
 
-def track_rows(z, locations, pilot_value=1.0 + 0j, mode=CPE):
-    """z [..., K] -> dict(data [..., Kd'], cpe [...], slope [...], U [...], usable [...]) in fp64."""
+def track_rows(z, locations, pilot_value=1.0 + 0j, mode=CPE, data_offsets=None):
+    """z [..., K] -> dict(data [..., Kd'], cpe [...], slope [...], U [...], usable [...]) in fp64.  Only the decision "usable" is
+    taken as the contract takes it, on |U|^2 = ur*ur + ui*ui evaluated in float32: a pilot sum whose square overflows float32 or
+    underflows it to 0 is not usable.  data_offsets replaces the data entries' bin offsets (tests that show what a wrong offset
+    does to their inputs)."""
     z = np.asarray(z).astype(np.complex128)
     K = z.shape[-1]
     pidx, pk, didx, dk = layout(K, locations)
+    if data_offsets is not None:
+        dk = np.asarray(data_offsets, dtype=np.float64)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        return _track(z, pidx, pk, didx, dk, pilot_value, mode)
+
+
+def _track(z, pidx, pk, didx, dk, pilot_value, mode):
     pv = complex(pilot_value)
     w = z[..., pidx] * np.conj(pv)
     U = np.zeros(z.shape[:-1], np.complex128)
     for p in range(len(pidx)):                                       # ascending p
         U = U + w[..., p]
+    ur, ui = U.real.astype(np.float32), U.imag.astype(np.float32)
+    n2f = ur * ur + ui * ui                                          # the contract's |U|^2: float32, may overflow or underflow to 0
     n2 = U.real ** 2 + U.imag ** 2
-    usable = np.isfinite(n2) & (n2 > 0)
+    usable = np.isfinite(n2f) & (n2f > 0)
     mag = np.sqrt(np.where(usable, n2, 1.0))
     c = np.where(usable, np.conj(U) / mag, 1.0 + 0j)
     cpe = np.where(usable, U / mag, 0j)
