@@ -4,33 +4,28 @@
 #include "capi_internal.hpp"
 
 namespace {
-// Index range of the kernels: 64-bit throughout; the bounds keep every product of them inside int64 and a row position in int.
-constexpr int64_t CSI_MAX_N = int64_t(1) << 31;        // segments
-constexpr int64_t CSI_MAX_LEN = int64_t(1) << 40;      // symbols per segment, n_seg*seg_stride and n_seg*csi_stride
-constexpr int64_t CSI_MAX_ROW = int64_t(1) << 30;      // entries per row
 bool csi_wanted(const ofdm_csi_out* o) { return o && (o->llr || o->sigma2 || o->n_used); }
 // what the arguments alone decide (no read of the handle, no device access); "" = fine
 const char* csi_bad_args(int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride, float rho,
                          int32_t modulation, int32_t noise_mode, double noise_var) {
     if (n_seg < 0 || rows < 0 || row_len < 0) return "negative count";
-    if (row_len > CSI_MAX_ROW || (row_len > 0 && rows > CSI_MAX_LEN / row_len)) return "index range exceeded (rows * row_len)";
+    if (row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len)) return "index range exceeded (rows * row_len)";
     if (seg_stride < rows * row_len) return "seg_stride < rows * row_len";
     if (csi_stride < row_len) return "csi_stride < row_len";
-    if (modulation != 2 && modulation != 4 && modulation != 6)
-        return "modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)";
+    if (!soft_mod_ok(modulation)) return "modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)";
     if (noise_mode != OFDM_CSI_NOISE_EST && noise_mode != OFDM_CSI_NOISE_GIVEN)
         return "noise_mode must be OFDM_CSI_NOISE_EST or OFDM_CSI_NOISE_GIVEN";
     if (noise_mode == OFDM_CSI_NOISE_GIVEN && !(std::isfinite(noise_var) && noise_var > 0.0))
         return "OFDM_CSI_NOISE_GIVEN needs a finite noise_var > 0";
     if (!(std::isfinite(rho) && rho >= 0.f)) return "rho must be finite and >= 0";
-    if (n_seg > CSI_MAX_N || (n_seg > 0 && (seg_stride > CSI_MAX_LEN / n_seg || csi_stride > CSI_MAX_LEN / n_seg)))
+    if (n_seg > SOFT_MAX_N || (n_seg > 0 && (seg_stride > SOFT_MAX_LEN / n_seg || csi_stride > SOFT_MAX_LEN / n_seg)))
         return "index range exceeded (batch beyond the kernels' index range)";
     return "";
 }
 const char* csi_bad_reserve(int64_t n_seg, int64_t rows, int64_t row_len) {
     if (n_seg < 0 || rows < 0 || row_len < 0) return "negative count";
-    if (n_seg > CSI_MAX_N || row_len > CSI_MAX_ROW || (row_len > 0 && rows > CSI_MAX_LEN / row_len) ||
-        (n_seg > 0 && row_len > CSI_MAX_LEN / n_seg))
+    if (n_seg > SOFT_MAX_N || row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len) ||
+        (n_seg > 0 && row_len > SOFT_MAX_LEN / n_seg))
         return "batch too large";
     return "";
 }
@@ -84,19 +79,8 @@ int ofdm_rx_reserve_csi(ofdm_rx* h, int64_t n_seg, int64_t rows, int64_t row_len
     const int64_t items = std::max(n_seg * seg_slices(rows * row_len), h->cap_csi_items);
     const int64_t tab = std::max(n_seg * row_len, h->cap_csi_tab);
     if (items <= h->cap_csi_items && tab <= h->cap_csi_tab) return OFDM_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->c_part_e, &h->c_part_n, &h->c_tab, &h->c_a);
-    h->cap_csi_items = h->cap_csi_tab = 0;
-    int rc = dev_alloc(&h->c_part_e, size_t(items));
-    if (rc == OFDM_OK) rc = dev_alloc(&h->c_part_n, size_t(items));
-    if (rc == OFDM_OK) rc = dev_alloc(&h->c_tab, size_t(tab));
-    if (rc == OFDM_OK) rc = dev_alloc(&h->c_a, size_t(tab));
-    if (rc != OFDM_OK) return rc;
-    h->cap_csi_items = items;
-    h->cap_csi_tab = tab;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_csi_items, items}, {&h->cap_csi_tab, tab}}, ws_buf(&h->c_part_e, size_t(items)),
+                  ws_buf(&h->c_part_n, size_t(items)), ws_buf(&h->c_tab, size_t(tab)), ws_buf(&h->c_a, size_t(tab)));
 }
 
 int ofdm_rx_csi_frames(ofdm_rx* h, int64_t n_frames, int32_t layout, float* d_csi, int64_t csi_stride, void* stream) {
@@ -111,7 +95,7 @@ int ofdm_rx_csi_frames(ofdm_rx* h, int64_t n_frames, int32_t layout, float* d_cs
     if (n_frames > h->last_frames)
         return fail(OFDM_ERR_INVALID, "ofdm_rx_csi_frames: %lld frames asked, the last ofdm_rx_demod_frames call had %lld",
                     static_cast<long long>(n_frames), static_cast<long long>(h->last_frames));
-    if (n_frames > CSI_MAX_N || (n_frames > 0 && csi_stride > CSI_MAX_LEN / n_frames))
+    if (n_frames > SOFT_MAX_N || (n_frames > 0 && csi_stride > SOFT_MAX_LEN / n_frames))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_csi_frames: index range exceeded");
     if (n_frames == 0 || n_out == 0) return OFDM_OK;
     if (!d_csi) return fail(OFDM_ERR_INVALID, "ofdm_rx_csi_frames: null d_csi");
@@ -137,14 +121,13 @@ int ofdm_demap_csi_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t
 int64_t ofdm_rx_demod_frames_csi(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                                  float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr, int32_t noise_mode,
                                  double noise_var, const ofdm_csi_out* out, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_csi: null handle");
-    if (!d_iq || n_frames < 0 || frame_len < 0 || frame_stride < frame_len)
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_csi: bad argument");
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, "ofdm_rx_demod_frames_csi");
+    if (open != OFDM_OK) return open;
     const bool want = csi_wanted(out);
     if (want && !d_eq) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_csi: the LLR stage needs d_eq (it reads it)");
     const RxDev& d = h->dev;
     const int mod = h->cfg.modulation;
-    const int64_t n_dsym = frame_len / d.L / (d.S + d.D) * d.D;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
     // the checks of the stages, made here first so that a bad call enqueues nothing
     const char* bad = demod_bad_args(d, n_frames, n_dsym, d_bits, bits_mode);
     if (!*bad && want) bad = csi_bad_args(n_frames, n_dsym, d.Kd, n_dsym * d.Kd, d.Kd, d.inv_snr_data, mod, noise_mode, noise_var);

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -251,6 +252,43 @@ int upload(T** p, const std::vector<T>& src, const char* what = INIT_FAILED) { r
 template <class... T>
 void free_dev(T**... p) { ((*p ? (void)hipFree(*p) : (void)0, *p = nullptr), ...); }
 
+// Before buffers of a handle are freed: its device current, its stream and then the device drained (work queued on a caller's
+// stream may still read them).
+template <class H>
+int drain(H* h) {
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    HIP_TRY(hipDeviceSynchronize());
+    return OFDM_OK;
+}
+
+// One workspace group of a handle replaced by a larger one: drain, free every buffer, zero every capacity, allocate, set the
+// capacities.  After a failed allocation every capacity of the group is 0 and every pointer null or still owned, so the next
+// growth or the destroy frees it.
+template <class T>
+struct WsBuf {
+    T** p;
+    size_t count;
+};
+template <class T>
+WsBuf<T> ws_buf(T** p, size_t count) { return {p, count}; }
+struct WsCap {
+    int64_t* cap;
+    int64_t value;
+};
+template <class H, class... T>
+int regrow(H* h, std::initializer_list<WsCap> caps, WsBuf<T>... bufs) {
+    const int drained = drain(h);
+    if (drained != OFDM_OK) return drained;
+    free_dev(bufs.p...);
+    for (const WsCap& c : caps) *c.cap = 0;
+    int rc = OFDM_OK;
+    ((rc = rc == OFDM_OK ? dev_alloc(bufs.p, bufs.count) : rc), ...);
+    if (rc != OFDM_OK) return rc;
+    for (const WsCap& c : caps) *c.cap = c.value;
+    return OFDM_OK;
+}
+
 // a workspace that must grow cannot do so inside a stream capture (growing synchronises and allocates)
 int refuse_growth_in_capture(hipStream_t s, const char* who, const char* reserve_name) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -306,6 +344,23 @@ const char* demod_bad_args(const RxDev& d, int64_t n_frames, int64_t n_dsym, con
     }
     return "";
 }
+// The opening of the calls that run stages behind ofdm_rx_demod_frames (ofdm_rx_demod_frames_*): the handle, then the batch
+// arguments with the buffers the call cannot do without (`bufs`); `what` is the text of the second refusal.
+int demod_stage_open(const ofdm_rx* h, bool bufs, int64_t n_frames, int64_t frame_stride, int64_t frame_len, const char* who,
+                     const char* what = "bad argument") {
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    if (!bufs || n_frames < 0 || frame_len < 0 || frame_stride < frame_len) return fail(OFDM_ERR_INVALID, "%s: %s", who, what);
+    return OFDM_OK;
+}
+// data symbols of a frame of frame_len samples: whole patterns of S sync and D data symbols
+int64_t frame_data_symbols(const RxDev& d, int64_t frame_len) { return frame_len / d.L / (d.S + d.D) * d.D; }
+
+// ---- the soft-output stages (segmented soft de-mapper, pilot tracking, channel-state-weighted LLRs, combining)
+// Index range of their kernels: 64-bit throughout; the bounds keep every product of them inside int64 and a row position in int.
+constexpr int64_t SOFT_MAX_N = int64_t(1) << 31;      // segments (combining: units = n_branch * n_seg)
+constexpr int64_t SOFT_MAX_LEN = int64_t(1) << 40;    // symbols per segment, n_seg*seg_stride and n_seg*csi_stride
+constexpr int64_t SOFT_MAX_ROW = int64_t(1) << 30;    // entries per row
+bool soft_mod_ok(int bits_per_symbol) { return bits_per_symbol == 2 || bits_per_symbol == 4 || bits_per_symbol == 6; }
 
 // ---- configuration checks the creates share (each sets the error text itself)
 int check_nfft(int n) {

@@ -4,13 +4,10 @@
 #include "capi_internal.hpp"
 
 namespace {
-// Index range of the kernels, as capi_csi.hip's with the units n_branch*n_seg in place of the segments.
-constexpr int64_t MRC_MAX_N = int64_t(1) << 31;        // units
-constexpr int64_t MRC_MAX_LEN = int64_t(1) << 40;      // symbols per segment, units*seg_stride and units*csi_stride
-constexpr int64_t MRC_MAX_ROW = int64_t(1) << 30;      // entries per row
+// Index range of the kernels: SOFT_MAX_* with the units n_branch*n_seg in place of the segments.
 static_assert(OFDM_MRC_MAX_BRANCHES == MRC_MAX_BRANCHES, "the header's branch limit is the kernels'");
 bool mrc_wanted(const ofdm_mrc_out* o) { return o && (o->llr || o->sym || o->weight); }
-bool mrc_units_ok(int32_t n_branch, int64_t n_seg) { return n_seg <= MRC_MAX_N / n_branch; }
+bool mrc_units_ok(int32_t n_branch, int64_t n_seg) { return n_seg <= SOFT_MAX_N / n_branch; }
 // what the arguments alone decide (no read of the handle, no device access); "" = fine.  given_only: the composite call, which
 // takes the variances from the host or estimates them.
 const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
@@ -18,11 +15,10 @@ const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t 
                          bool composite) {
     if (n_seg < 0 || rows < 0 || row_len < 0) return "negative count";
     if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES) return "n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES";
-    if (row_len > MRC_MAX_ROW || (row_len > 0 && rows > MRC_MAX_LEN / row_len)) return "index range exceeded (rows * row_len)";
+    if (row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len)) return "index range exceeded (rows * row_len)";
     if (seg_stride < rows * row_len) return "seg_stride < rows * row_len";
     if (csi_stride < row_len) return "csi_stride < row_len";
-    if (modulation != 2 && modulation != 4 && modulation != 6)
-        return "modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)";
+    if (!soft_mod_ok(modulation)) return "modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)";
     if (composite) {
         if (noise_mode != OFDM_MRC_NOISE_GIVEN && noise_mode != OFDM_MRC_NOISE_EST)
             return "noise_mode must be OFDM_MRC_NOISE_GIVEN or OFDM_MRC_NOISE_EST";
@@ -38,7 +34,7 @@ const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t 
     if (!(std::isfinite(rho) && rho >= 0.f)) return "rho must be finite and >= 0";
     if (!mrc_units_ok(n_branch, n_seg)) return "index range exceeded (batch beyond the kernels' index range)";
     const int64_t units = n_branch * n_seg;
-    if (units > 0 && (seg_stride > MRC_MAX_LEN / units || csi_stride > MRC_MAX_LEN / units))
+    if (units > 0 && (seg_stride > SOFT_MAX_LEN / units || csi_stride > SOFT_MAX_LEN / units))
         return "index range exceeded (batch beyond the kernels' index range)";
     return "";
 }
@@ -89,8 +85,8 @@ int ofdm_rx_reserve_mrc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t row
     if (n_seg < 0 || rows < 0 || row_len < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: negative count");
     if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES)
         return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES");
-    if (!mrc_units_ok(n_branch, n_seg) || row_len > MRC_MAX_ROW || (row_len > 0 && rows > MRC_MAX_LEN / row_len) ||
-        (n_seg > 0 && row_len > MRC_MAX_LEN / (n_branch * n_seg)))
+    if (!mrc_units_ok(n_branch, n_seg) || row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len) ||
+        (n_seg > 0 && row_len > SOFT_MAX_LEN / (n_branch * n_seg)))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: batch too large");
     const int64_t units = n_branch * n_seg;
     // the composite call runs the |H|^2 rows and the noise estimate of the channel-state-weighted LLR stage over the units
@@ -99,17 +95,8 @@ int ofdm_rx_reserve_mrc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t row
     const int64_t tab = std::max(units * row_len, h->cap_mrc_tab);
     const int64_t n_units = std::max(units, h->cap_mrc_units);
     if (tab <= h->cap_mrc_tab && n_units <= h->cap_mrc_units) return OFDM_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->m_tab, &h->m_sigma2);
-    h->cap_mrc_tab = h->cap_mrc_units = 0;
-    int rc = dev_alloc(&h->m_tab, size_t(tab));
-    if (rc == OFDM_OK) rc = dev_alloc(&h->m_sigma2, size_t(n_units));
-    if (rc != OFDM_OK) return rc;
-    h->cap_mrc_tab = tab;
-    h->cap_mrc_units = n_units;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_mrc_tab, tab}, {&h->cap_mrc_units, n_units}}, ws_buf(&h->m_tab, size_t(tab)),
+                  ws_buf(&h->m_sigma2, size_t(n_units)));
 }
 
 int ofdm_combine_csi_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len,
@@ -133,16 +120,15 @@ int ofdm_combine_csi_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, in
 int64_t ofdm_rx_demod_frames_mrc(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames, int64_t frame_stride,
                                  int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode, const double* h_noise_var,
                                  const ofdm_mrc_out* out, double* d_sigma2_out, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: null handle");
-    if (!d_iq || n_frames < 0 || frame_len < 0 || frame_stride < frame_len)
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: bad argument");
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, "ofdm_rx_demod_frames_mrc");
+    if (open != OFDM_OK) return open;
     if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES || !mrc_units_ok(n_branch, n_frames))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES");
     if (!d_eq) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: the combiner needs d_eq (it reads it)");
     const RxDev& d = h->dev;
     const int mod = h->cfg.modulation;
     const int64_t units = n_branch * n_frames;
-    const int64_t n_dsym = frame_len / d.L / (d.S + d.D) * d.D;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
     // the checks of the stages, made here first so that a bad call enqueues nothing
     const char* bad = demod_bad_args(d, units, n_dsym, nullptr, OFDM_BITS_NONE);
     if (!*bad)

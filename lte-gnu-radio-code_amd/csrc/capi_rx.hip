@@ -161,19 +161,10 @@ int ofdm_rx_create(const ofdm_rx_cfg* c, ofdm_rx** out) {
 int ofdm_rx_reserve(ofdm_rx* h, int64_t n_frames) {
     if (!h || n_frames < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve: bad argument");
     if (n_frames <= h->cap_frames) return OFDM_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime);
-    h->cap_frames = 0;
-    h->last_frames = 0;
-    int rc = dev_alloc(&h->f_tsr, size_t(n_frames) * 4);
-    if (rc == OFDM_OK) rc = dev_alloc(&h->f_H, size_t(n_frames) * h->dev.nfft);
-    if (rc == OFDM_OK) rc = dev_alloc(&h->f_gain, size_t(n_frames) * h->dev.Kd);
-    if (rc == OFDM_OK) rc = dev_alloc(&h->f_htime, size_t(n_frames) * h->dev.nfft);
-    if (rc != OFDM_OK) return rc;
-    h->cap_frames = n_frames;
-    return OFDM_OK;
+    h->last_frames = 0;                  // the rows of f_H go with the old buffer: none until the next ofdm_rx_demod_frames
+    return regrow(h, {{&h->cap_frames, n_frames}}, ws_buf(&h->f_tsr, size_t(n_frames) * 4),
+                  ws_buf(&h->f_H, size_t(n_frames) * h->dev.nfft), ws_buf(&h->f_gain, size_t(n_frames) * h->dev.Kd),
+                  ws_buf(&h->f_htime, size_t(n_frames) * h->dev.nfft));
 }
 
 int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride,

@@ -32,15 +32,12 @@ extern "C" {
 // ---- segmented soft de-mapper (one sigma per segment = per frame of the batch path)
 }  // extern "C"
 namespace {
-// Index range of the segmented kernels: 64-bit throughout; the bounds keep every product of them inside int64.
-constexpr int64_t SEG_MAX_N = int64_t(1) << 31;      // segments
-constexpr int64_t SEG_MAX_LEN = int64_t(1) << 40;    // symbols per segment, and n_seg*seg_stride
 bool soft_wanted(const ofdm_soft_out* o) { return o && (o->soft0 || o->soft1 || o->llr || o->sigma); }
 // argument check shared by both entry points (no device access); "" = fine
 const char* soft_bad_args(int64_t n_seg, int64_t seg_len, int64_t seg_stride) {
     if (n_seg < 0 || seg_len < 0) return "negative count";
     if (seg_stride < seg_len) return "seg_stride < seg_len";
-    if (n_seg > SEG_MAX_N || seg_len > SEG_MAX_LEN || (n_seg > 0 && seg_stride > SEG_MAX_LEN / n_seg))
+    if (n_seg > SOFT_MAX_N || seg_len > SOFT_MAX_LEN || (n_seg > 0 && seg_stride > SOFT_MAX_LEN / n_seg))
         return "batch beyond the kernels' index range";
     return "";
 }
@@ -72,18 +69,10 @@ extern "C" {
 
 int ofdm_rx_reserve_soft(ofdm_rx* h, int64_t n_seg, int64_t seg_len) {
     if (!h || n_seg < 0 || seg_len < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_soft: bad argument");
-    if (n_seg > SEG_MAX_N || seg_len > SEG_MAX_LEN) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_soft: batch too large");
+    if (n_seg > SOFT_MAX_N || seg_len > SOFT_MAX_LEN) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_soft: batch too large");
     const int64_t need = n_seg * seg_slices(seg_len);
     if (need <= h->cap_seg_partial) return OFDM_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->f_seg_partial);
-    h->cap_seg_partial = 0;
-    const int rc = dev_alloc(&h->f_seg_partial, size_t(need));
-    if (rc != OFDM_OK) return rc;
-    h->cap_seg_partial = need;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_seg_partial, need}}, ws_buf(&h->f_seg_partial, size_t(need)));
 }
 
 int ofdm_demap_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg_len, int64_t seg_stride, int32_t modulation,
@@ -91,7 +80,7 @@ int ofdm_demap_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: null handle");
     const char* bad = soft_bad_args(n_seg, seg_len, seg_stride);
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: %s", bad);
-    if (modulation != 2 && modulation != 4 && modulation != 6)
+    if (!soft_mod_ok(modulation))
         return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)");
     if (n_seg == 0 || seg_len == 0 || !soft_wanted(out)) return OFDM_OK;
     if (!d_sym) return fail(OFDM_ERR_INVALID, "ofdm_demap_frames: null d_sym");
@@ -105,16 +94,15 @@ int ofdm_demap_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg
 int64_t ofdm_rx_demod_frames_soft(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                                   float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr, const ofdm_soft_out* soft,
                                   void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: null handle");
-    if (!d_iq || n_frames < 0 || frame_len < 0 || frame_stride < frame_len)
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: bad argument");
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, "ofdm_rx_demod_frames_soft");
+    if (open != OFDM_OK) return open;
     const bool want = soft_wanted(soft);
     if (want && !d_eq) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: soft outputs need d_eq (the soft pass reads it)");
     const int mod = h->cfg.modulation;
-    if (want && mod != 2 && mod != 4 && mod != 6)
+    if (want && !soft_mod_ok(mod))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_soft: soft metrics need QPSK, 16-QAM or 64-QAM");
     const RxDev& d = h->dev;
-    const int64_t n_dsym = frame_len / d.L / (d.S + d.D) * d.D;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
     const int64_t seg_len = n_dsym * d.Kd;
     // the checks ofdm_rx_demod_frames makes, made here first so that a bad call enqueues nothing
     const char* bad = demod_bad_args(d, n_frames, n_dsym, d_bits, bits_mode);
@@ -153,12 +141,12 @@ const char* pilot_bad_args(const ofdm_rx* h, int64_t n_seg, int64_t rows, int64_
     if (h->n_pilots == 0) return "no pilots set (ofdm_rx_set_pilots)";
     if (mode == OFDM_PILOT_CPE_SLOPE && h->n_pilots < 2) return "OFDM_PILOT_CPE_SLOPE needs at least two pilots";
     const int64_t K = h->dev.Kd;
-    if (rows > SEG_MAX_LEN / K || seg_stride < rows * K) return "seg_stride < rows * num_data_bins";
-    if (n_seg >= SEG_MAX_N || (n_seg > 0 && (seg_stride > SEG_MAX_LEN / n_seg || rows > PILOT_MAX_ROWS / n_seg)))
+    if (rows > SOFT_MAX_LEN / K || seg_stride < rows * K) return "seg_stride < rows * num_data_bins";
+    if (n_seg >= SOFT_MAX_N || (n_seg > 0 && (seg_stride > SOFT_MAX_LEN / n_seg || rows > PILOT_MAX_ROWS / n_seg)))
         return "batch beyond the kernels' index range";
     if (out && out->bits) {
         const int mod = h->cfg.modulation;
-        if (mod != 2 && mod != 4 && mod != 6) return "hard bits need QPSK, 16-QAM or 64-QAM";
+        if (!soft_mod_ok(mod)) return "hard bits need QPSK, 16-QAM or 64-QAM";
         if (out->bits_mode == OFDM_BITS_PACKED && ((K - h->n_pilots) * mod) % 8 != 0)
             return "packed bits need (num_data_bins - n_pilots) * bits per symbol % 8 == 0";
     }
@@ -222,9 +210,8 @@ int ofdm_rx_set_pilots(ofdm_rx* h, const int32_t* h_locations, int32_t n_pilots,
         if (idx[size_t(p)] == idx[size_t(p - 1)]) return fail(OFDM_ERR_INVALID, "pilot locations must be distinct");
     if (n_pilots > 0 && !(std::isfinite(pilot_re) && std::isfinite(pilot_im) && (pilot_re != 0.f || pilot_im != 0.f)))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_set_pilots: pilot value must be finite and non-zero");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
+    const int drained = drain(h);
+    if (drained != OFDM_OK) return drained;
     free_dev(&h->p_idx, &h->p_k, &h->p_src);
     h->n_pilots = 0;
     if (n_pilots == 0) return OFDM_OK;
@@ -259,19 +246,11 @@ int ofdm_rx_set_pilots(ofdm_rx* h, const int32_t* h_locations, int32_t n_pilots,
 
 int ofdm_rx_reserve_pilots(ofdm_rx* h, int64_t n_seg, int64_t rows) {
     if (!h || n_seg < 0 || rows < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_pilots: bad argument");
-    if (n_seg >= SEG_MAX_N || (n_seg > 0 && rows > PILOT_MAX_ROWS / n_seg))
+    if (n_seg >= SOFT_MAX_N || (n_seg > 0 && rows > PILOT_MAX_ROWS / n_seg))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_pilots: batch too large");
     const int64_t need = n_seg * rows;
     if (need <= h->cap_usum) return OFDM_OK;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->f_usum);
-    h->cap_usum = 0;
-    const int rc = dev_alloc(&h->f_usum, size_t(need));
-    if (rc != OFDM_OK) return rc;
-    h->cap_usum = need;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_usum, need}}, ws_buf(&h->f_usum, size_t(need)));
 }
 
 int ofdm_pilot_track_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t seg_stride,
@@ -293,11 +272,11 @@ int ofdm_pilot_track_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64
 int64_t ofdm_rx_demod_frames_pilots(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
                                     float* d_eq, int32_t* d_tsr, int32_t mode, const ofdm_pilot_out* out, const ofdm_soft_out* soft,
                                     void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_pilots: null handle");
-    if (!d_iq || !d_eq || n_frames < 0 || frame_len < 0 || frame_stride < frame_len)
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_pilots: bad argument (d_eq is required: the pilot stage reads it)");
+    const int open = demod_stage_open(h, d_iq && d_eq, n_frames, frame_stride, frame_len, "ofdm_rx_demod_frames_pilots",
+                                      "bad argument (d_eq is required: the pilot stage reads it)");
+    if (open != OFDM_OK) return open;
     const RxDev& d = h->dev;
-    const int64_t n_dsym = frame_len / d.L / (d.S + d.D) * d.D;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
     // the checks of the three stages, made here first so that a bad call enqueues nothing
     const char* bad = demod_bad_args(d, n_frames, n_dsym, nullptr, OFDM_BITS_NONE);
     if (!*bad) bad = pilot_bad_args(h, n_frames, n_dsym, n_dsym * d.Kd, d.D, mode, out);
@@ -307,8 +286,7 @@ int64_t ofdm_rx_demod_frames_pilots(ofdm_rx* h, const float* d_iq, int64_t n_fra
     if (want_soft) {
         if (!want || !out->data)
             return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_pilots: soft outputs need out->data (the soft pass reads it)");
-        const int mod = h->cfg.modulation;
-        if (mod != 2 && mod != 4 && mod != 6)
+        if (!soft_mod_ok(h->cfg.modulation))
             return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_pilots: soft metrics need QPSK, 16-QAM or 64-QAM");
         bad = soft_bad_args(n_frames, seg_len, seg_len);
         if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_pilots: %s", bad);

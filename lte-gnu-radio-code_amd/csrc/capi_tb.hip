@@ -135,14 +135,7 @@ int64_t rx_turbo_es_floats(const ofdm_tb_geom& g, int64_t n_tb) {
 template <class H>
 int tb_grow(H* h, int64_t bytes) {
     if (bytes <= h->cap_tb) return OFDM_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->tb_ws);
-    h->cap_tb = 0;
-    const int rc = dev_alloc(&h->tb_ws, size_t(bytes));
-    if (rc != OFDM_OK) return rc;
-    h->cap_tb = bytes;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_tb, bytes}}, ws_buf(&h->tb_ws, size_t(bytes)));
 }
 
 int rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z, bool es, const char* who) {

@@ -34,14 +34,7 @@ int turbo_ensure(ofdm_rx* h, int64_t n_blocks, int32_t K, hipStream_t s) {
 // both decoders share the handle's workspace: it holds `need` floats afterwards, and only grows
 int turbo_grow(ofdm_rx* h, int64_t need) {
     if (need <= h->cap_turbo) return OFDM_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
-    free_dev(&h->t_ws);
-    h->cap_turbo = 0;
-    const int rc = dev_alloc(&h->t_ws, size_t(need));
-    if (rc != OFDM_OK) return rc;
-    h->cap_turbo = need;
-    return OFDM_OK;
+    return regrow(h, {{&h->cap_turbo, need}}, ws_buf(&h->t_ws, size_t(need)));
 }
 const char* turbo_bad_reserve(int64_t n_blocks, int32_t K) {
     if (!turbo_valid_k(K)) return TURBO_BAD_K;

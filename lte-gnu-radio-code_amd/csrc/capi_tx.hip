@@ -211,9 +211,8 @@ int ofdm_tx_set_pilots(ofdm_tx* h, const int32_t* h_locations, int32_t n_pilots,
     std::sort(idx.begin(), idx.end());
     for (int p = 1; p < n_pilots; ++p)
         if (idx[size_t(p)] == idx[size_t(p - 1)]) return fail(OFDM_ERR_INVALID, "pilot locations must be distinct");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipDeviceSynchronize());
+    const int drained = drain(h);
+    if (drained != OFDM_OK) return drained;
     free_dev(&h->d_pilots);
     h->n_pilots = 0;
     const int rc = upload(&h->d_pilots, idx);

@@ -10,59 +10,11 @@
 // Every float32 product, sum and quotient below is rounded on its own (contraction off), so the outputs are those of the NumPy
 // restatement in tests/csi_ref.py bit for bit and do not depend on the path a symbol takes.
 #include "ofdm_launch.hpp"
+#include "soft_device.hpp"
 
 namespace ofdm {
 
 namespace {
-
-__device__ __forceinline__ bool csi_finite(float x) { return fabsf(x) < __builtin_inff(); }
-
-__device__ __forceinline__ float4 csi_load16(const float* p) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-    return float4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void csi_store16(float* p, float4 v) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
-// One axis: d[j] = min over the levels with axis bit j = 1 of (x-l)^2 minus the same over bit j = 0, and m = the smallest
-// (x-l)^2 of all.  Levels and labels are those of rx_demap.hip: +-0.70710678 for QPSK (bit 0 <-> the positive level), else
-// l_q = float(2q - (M-1)) * u with the TS 36.211 7.1 labels of Pam<BPS>.
-template <int MOD>
-__device__ __forceinline__ void csi_axis(float x, float (&d)[MOD / 2], float& m) {
-#pragma clang fp contract(off)
-    if constexpr (MOD == 2) {
-        constexpr float c = 0.70710678118654752f;
-        const float p = (x - c) * (x - c), n = (x - (-c)) * (x - (-c));
-        d[0] = n - p;
-        m = fminf(p, n);
-    } else {
-        constexpr int M = MOD == 4 ? 4 : 8, NB = MOD / 2;
-        const float u = MOD == 4 ? 0.31622776601683794f : 0.15430334996209191f;
-        float m0[NB], m1[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) m0[j] = m1[j] = __builtin_inff();
-#pragma unroll
-        for (int q = 0; q < M; ++q) {
-            const int lv = 2 * q - (M - 1), am = lv < 0 ? -lv : lv;
-            const float l = float(lv) * u;
-            const float e = (x - l) * (x - l);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const bool one = j == 0 ? lv < 0 : (MOD == 4 ? am == 3 : (j == 1 ? am > 4 : (am == 1 || am == 7)));
-                if (one)
-                    m1[j] = fminf(m1[j], e);
-                else
-                    m0[j] = fminf(m0[j], e);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) d[j] = m1[j] - m0[j];
-        m = fminf(m0[0], m1[0]);
-    }
-}
 
 // One symbol with its entry's s (0: the entry is an erasure): the usable test, d[] in ofdm_demap's bit order (b0 real axis, b1
 // imaginary axis, b2 real axis, ...) and m = |u - nearest point|^2.
@@ -70,10 +22,10 @@ template <int MOD>
 __device__ __forceinline__ bool csi_symbol(cf z, float s, float (&d)[MOD], float& m) {
 #pragma clang fp contract(off)
     const float ur = z.x * s, ui = z.y * s;
-    const bool ok = s != 0.f && csi_finite(z.x) && csi_finite(z.y) && (z.x != 0.f || z.y != 0.f) && csi_finite(ur) && csi_finite(ui);
+    const bool ok = s != 0.f && soft_finite(z.x) && soft_finite(z.y) && (z.x != 0.f || z.y != 0.f) && soft_finite(ur) && soft_finite(ui);
     float dr[MOD / 2], di[MOD / 2], mr, mi;
-    csi_axis<MOD>(ur, dr, mr);
-    csi_axis<MOD>(ui, di, mi);
+    soft_axis<MOD>(ur, dr, mr);
+    soft_axis<MOD>(ui, di, mi);
 #pragma unroll
     for (int j = 0; j < MOD / 2; ++j) {
         d[2 * j] = dr[j];
@@ -92,28 +44,9 @@ __device__ __forceinline__ bool csi_llr(cf z, float2 t, float (&o)[MOD]) {
 #pragma unroll
     for (int b = 0; b < MOD; ++b) {
         const float v = t.y * d[b];
-        o[b] = (ok && csi_finite(v)) ? v : 0.f;
+        o[b] = (ok && soft_finite(v)) ? v : 0.f;
     }
     return ok;
-}
-
-__device__ __forceinline__ int csi_wrap(int j, int rl) { return j >= rl ? j - rl : j; }
-
-// sums over the workgroup (256 lanes) in a fixed order: butterfly per wave, then the four wave sums; every lane gets the totals.
-// The caller puts a barrier between two uses of the same arrays.
-__device__ __forceinline__ void csi_block_sum(double& v, long long& n, double (&sh)[4], long long (&shn)[4]) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        v += __shfl_xor(v, m, 64);
-        n += __shfl_xor(n, m, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6] = v;
-        shn[threadIdx.x >> 6] = n;
-    }
-    __syncthreads();
-    v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    n = (shn[0] + shn[1]) + (shn[2] + shn[3]);
 }
 
 }  // namespace
@@ -125,13 +58,13 @@ __global__ void __launch_bounds__(256) csi_table_kernel(CsiArgs a) {
 #pragma clang fp contract(off)
     const int64_t n = a.n_seg * a.row_len;
     const float w_den = float(a.noise_var);
-    const bool w_ok = csi_finite(w_den) && w_den > 0.f;
+    const bool w_ok = soft_finite(w_den) && w_den > 0.f;
     for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
         const int64_t s = i / a.row_len;
         const int j = int(i - s * a.row_len);
         const float av = a.csi[s * a.csi_stride + j];
         const float sv = (av + a.rho) / av;
-        const bool ok = csi_finite(av) && av > 0.f && csi_finite(sv);
+        const bool ok = soft_finite(av) && av > 0.f && soft_finite(sv);
         a.tab[i] = float2{ok ? sv : 0.f, a.est ? av : (w_ok ? av / w_den : __builtin_nanf(""))};
     }
 }
@@ -164,7 +97,7 @@ __global__ void __launch_bounds__(256) csi_noise_kernel(CsiArgs a) {
             const int i0 = 2 * (k * 256 + int(threadIdx.x));
             z[k][0] = z[k][1] = cf{0.f, 0.f};                                             // z = 0 is not usable: nothing is added
             if (wide && i0 + 1 < len) {
-                const float4 v = csi_load16(reinterpret_cast<const float*>(p + i0));
+                const float4 v = load_stream16(reinterpret_cast<const float*>(p + i0));
                 z[k][0] = cf{v.x, v.y};
                 z[k][1] = cf{v.z, v.w};
             } else {
@@ -172,8 +105,8 @@ __global__ void __launch_bounds__(256) csi_noise_kernel(CsiArgs a) {
                 if (i0 + 1 < len) z[k][1] = p[i0 + 1];
             }
             t[k][0] = tab[j];
-            t[k][1] = tab[csi_wrap(j + 1, rl)];
-            j = csi_wrap(j + step, rl);
+            t[k][1] = tab[row_wrap(j + 1, rl)];
+            j = row_wrap(j + step, rl);
         }
 #pragma unroll
         for (int k = 0; k < STEPS; ++k) {
@@ -182,13 +115,13 @@ __global__ void __launch_bounds__(256) csi_noise_kernel(CsiArgs a) {
                 float d[MOD], m;
                 const bool ok = csi_symbol<MOD>(z[k][e], t[k][e].x, d, m);
                 const float en = t[k][e].y * m;
-                if (ok && csi_finite(en)) {
+                if (ok && soft_finite(en)) {
                     acc += double(en);
                     cnt += 1;
                 }
             }
         }
-        csi_block_sum(acc, cnt, sh, shn);
+        block_sum(acc, cnt, sh, shn);
         if (threadIdx.x == 0) {
             a.part_e[w] = acc;
             a.part_n[w] = cnt;
@@ -210,7 +143,7 @@ __global__ void __launch_bounds__(256) csi_finish_kernel(CsiArgs a, int counts) 
                 if (a.est) acc += a.part_e[s * a.n_slices + i];
                 cnt += a.part_n[s * a.n_slices + i];
             }
-            csi_block_sum(acc, cnt, sh, shn);
+            block_sum(acc, cnt, sh, shn);
         }
         const double sigma2 = a.est ? (cnt > 0 ? acc / double(cnt) : 0.0) : a.noise_var;
         if (threadIdx.x == 0) {
@@ -219,7 +152,7 @@ __global__ void __launch_bounds__(256) csi_finish_kernel(CsiArgs a, int counts) 
         }
         if (a.est) {
             const float w_den = float(sigma2);
-            const bool w_ok = csi_finite(w_den) && w_den > 0.f;
+            const bool w_ok = soft_finite(w_den) && w_den > 0.f;
             float2* tab = a.tab + s * a.row_len;
             for (int j = threadIdx.x; j < a.row_len; j += 256) tab[j].y = w_ok ? tab[j].y / w_den : __builtin_nanf("");
         }
@@ -258,26 +191,25 @@ __global__ void __launch_bounds__(256) csi_llr_kernel(CsiArgs a) {
                 done = len & ~1;
                 int j = int((j0 + 2u * threadIdx.x) % unsigned(rl));
                 for (int g = threadIdx.x; 2 * g < done; g += 256) {
-                    const float4 v = csi_load16(reinterpret_cast<const float*>(p + 2 * g));
-                    const float2 t0 = tab[j], t1 = tab[csi_wrap(j + 1, rl)];
+                    const float4 v = load_stream16(reinterpret_cast<const float*>(p + 2 * g));
+                    const float2 t0 = tab[j], t1 = tab[row_wrap(j + 1, rl)];
                     float o0[2], o1[2];
                     cnt += csi_llr<2>(cf{v.x, v.y}, t0, o0);
                     cnt += csi_llr<2>(cf{v.z, v.w}, t1, o1);
-                    csi_store16(ql + 4 * g, float4{o0[0], o0[1], o1[0], o1[1]});
-                    j = csi_wrap(j + step512, rl);
+                    store_stream16(ql + 4 * g, float4{o0[0], o0[1], o1[0], o1[1]});
+                    j = row_wrap(j + step512, rl);
                 }
             }
         } else if constexpr (MOD == 4) {
             if (wide) {
                 done = len;
-                typedef float f2 __attribute__((ext_vector_type(2)));
                 int j = int((j0 + threadIdx.x) % unsigned(rl));
                 for (int i = threadIdx.x; i < len; i += 256) {
-                    const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p + i));
+                    const float2 v = load_stream8(reinterpret_cast<const float*>(p + i));
                     float o[4];
                     cnt += csi_llr<4>(cf{v.x, v.y}, tab[j], o);
-                    csi_store16(ql + 4 * i, float4{o[0], o[1], o[2], o[3]});
-                    j = csi_wrap(j + step256, rl);
+                    store_stream16(ql + 4 * i, float4{o[0], o[1], o[2], o[3]});
+                    j = row_wrap(j + step256, rl);
                 }
             }
         } else {
@@ -288,24 +220,13 @@ __global__ void __launch_bounds__(256) csi_llr_kernel(CsiArgs a) {
                 float* st = stage[wave];
                 int j = int((j0 + unsigned(wave * TILE + 2 * lane)) % unsigned(rl));
                 for (int t = wave; t < n_tiles; t += 4) {
-                    const float4 v = csi_load16(reinterpret_cast<const float*>(p + t * TILE + 2 * lane));
-                    const float2 t0 = tab[j], t1 = tab[csi_wrap(j + 1, rl)];
+                    const float4 v = load_stream16(reinterpret_cast<const float*>(p + t * TILE + 2 * lane));
+                    const float2 t0 = tab[j], t1 = tab[row_wrap(j + 1, rl)];
                     float x[6], y[6];
                     cnt += csi_llr<6>(cf{v.x, v.y}, t0, x);                                 // symbol 2*lane of the tile
                     cnt += csi_llr<6>(cf{v.z, v.w}, t1, y);                                 // symbol 2*lane + 1
-                    // through the wave's 3 KB: 12 floats per lane in, 3 x 16 B per lane out
-                    float4* wr = reinterpret_cast<float4*>(st + lane * 12);
-                    wr[0] = float4{x[0], x[1], x[2], x[3]};
-                    wr[1] = float4{x[4], x[5], y[0], y[1]};
-                    wr[2] = float4{y[2], y[3], y[4], y[5]};
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // wave-local exchange: in order per wave
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const int piece = k * 64 + lane;
-                        csi_store16(ql + int64_t(t) * (TILE * 6) + 4 * piece, *reinterpret_cast<const float4*>(st + 4 * piece));
-                    }
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    // reads done before the stage is rewritten
-                    j = csi_wrap(j + step512, rl);
+                    store_tile64(ql, t, lane, st, x, y);
+                    j = row_wrap(j + step512, rl);
                 }
             }
         }
@@ -318,12 +239,12 @@ __global__ void __launch_bounds__(256) csi_llr_kernel(CsiArgs a) {
 #pragma unroll
                     for (int b = 0; b < MOD; ++b) ql[int64_t(i) * MOD + b] = o[b];
                 }
-                j = csi_wrap(j + step256, rl);
+                j = row_wrap(j + step256, rl);
             }
         }
         if constexpr (COUNT) {
             double unused = 0.0;
-            csi_block_sum(unused, cnt, sh, shn);
+            block_sum(unused, cnt, sh, shn);
             if (threadIdx.x == 0) a.part_n[w] = cnt;
             __syncthreads();                                                              // shn is reused by the next item
         }

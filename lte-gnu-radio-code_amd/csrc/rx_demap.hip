@@ -2,6 +2,7 @@
 // (reference: LEGACY/gr-ofdm-rx/python/BitRecovery.py:66-157), whole buffers and per-frame segments.
 #include "ofdm_launch.hpp"
 #include "demap_hard.hpp"
+#include "soft_device.hpp"
 
 namespace ofdm {
 
@@ -29,14 +30,6 @@ __device__ __forceinline__ void qpsk_nearest(cf z, bool& re_pos, bool& im_pos, c
     im_pos = (z.y >= 0.f);
     constexpr float c = 0.70710678118654752f;
     e = cf{z.x - (re_pos ? c : -c), z.y - (im_pos ? c : -c)};                            // :93-98
-}
-
-__device__ __forceinline__ void store_stream16(float* p, float4 v);
-// 16-byte load of data this kernel reads once
-__device__ __forceinline__ float4 load_stream16(const float* p) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-    return float4{v.x, v.y, v.z, v.w};
 }
 
 // pass 2: llrp0 / llrp1 (BitRecovery.py:102-125)
@@ -197,12 +190,6 @@ __global__ void __launch_bounds__(256) demap_pass1_kernel(DemapArgs a) {
     }
 }
 
-// 16-byte store of data that is written once and not read again by this kernel
-__device__ __forceinline__ void store_stream16(float* p, float4 v) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-
 template <int BPS>
 __global__ void __launch_bounds__(256) demap_soft_qam_kernel(DemapArgs a) {
     __shared__ double sh_tot;
@@ -314,17 +301,7 @@ __global__ void __launch_bounds__(256) demap_soft_qam64_kernel(DemapArgs a) {
 // ---- segmented soft de-mapper (ofdm_demap_frames): the metrics above with one sigma per segment (one frame of the batch).
 // Work item w = (segment w / n_slices, slice w % n_slices), workgroups loop over the items with the grid as stride.  Nothing is
 // added atomically: pass 1 writes one double per item, pass 2 adds a segment's partials in a fixed order, so a segment's outputs
-// are the same bits alone, in any batch and on every call.
-
-// sum of a double over the workgroup (256 lanes): butterfly per wave, then the four wave sums in order.  Every lane gets the
-// total; `sh` must not be touched by another reduction until the caller's next barrier.
-__device__ __forceinline__ double seg_block_sum(double v, double (&sh)[4]) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
+// are the same bits alone, in any batch and on every call (block_sum of soft_device.hpp).
 
 // Pass 1: a thread takes groups of FOUR consecutive symbols (two 16 B non-temporal loads where the slice is 16-byte aligned,
 // else four 8 B loads) and adds their distances to its running double sum ONE BY ONE, in the same order on both paths: the
@@ -359,7 +336,7 @@ __global__ void __launch_bounds__(256) demap_seg_dmin_kernel(SegDemapArgs a) {
             for (int e = 0; e < 4; ++e)
                 if (i0 + e < len) acc += double(demap_dmin<MOD>(z[e]));
         }
-        const double tot = seg_block_sum(acc, sh);
+        const double tot = block_sum(acc, sh);
         if (threadIdx.x == 0) a.partial[w] = tot;
         __syncthreads();
     }
@@ -397,7 +374,7 @@ __device__ __forceinline__ void seg_metrics(cf z, float hf, float (&o0)[MOD], fl
 }
 
 // Pass 2: sigma of the item's segment from its partials (each lane adds partials lane, lane+256, ... in order, then
-// seg_block_sum), hf = -0.5/sigma^2 as ofdm_demap, then the slice's requested arrays (OUTS = SEG_OUT_* bits; OUTS == 0: sigma
+// block_sum), hf = -0.5/sigma^2 as ofdm_demap, then the slice's requested arrays (OUTS = SEG_OUT_* bits; OUTS == 0: sigma
 // only, one item per segment).  llr = llrp0 - llrp1 of the two rounded values: the pragma keeps the compiler from contracting
 // hf*d0 - hf*d1 into an fma.  QPSK: two symbols per lane (16 B load, 16 B store per array); 16-QAM: one symbol per lane (8 B
 // load, 16 B store per array); 64-QAM: a wave's tile of 128 symbols through LDS as demap_soft_qam64_kernel, one array after
@@ -417,7 +394,7 @@ __global__ void __launch_bounds__(256) demap_seg_soft_kernel(SegDemapArgs a) {
         const double* part = a.partial + s * a.n_slices;
         double acc = 0.0;
         for (int64_t i = threadIdx.x; i < a.n_slices; i += 256) acc += part[i];
-        const double sigma = 0.7071067811865476 * (seg_block_sum(acc, sh) / double(a.seg_len));
+        const double sigma = 0.7071067811865476 * (block_sum(acc, sh) / double(a.seg_len));
         const float hf = float(-0.5 / (sigma * sigma));
         if (sl == 0 && threadIdx.x == 0 && a.sigma) a.sigma[s] = sigma;
         if constexpr (OUTS != 0) {
@@ -455,9 +432,8 @@ __global__ void __launch_bounds__(256) demap_seg_soft_kernel(SegDemapArgs a) {
             } else if constexpr (MOD == 4) {
                 if (wide) {
                     done = len;
-                    typedef float f2 __attribute__((ext_vector_type(2)));
                     for (int i = threadIdx.x; i < len; i += 256) {
-                        const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p + i));
+                        const float2 v = load_stream8(reinterpret_cast<const float*>(p + i));
                         float o0[4], o1[4];
                         seg_metrics<4>(cf{v.x, v.y}, hf, o0, o1);
                         if constexpr (S0) store_stream16(q0 + 4 * i, float4{o0[0], o0[1], o0[2], o0[3]});
@@ -477,21 +453,8 @@ __global__ void __launch_bounds__(256) demap_seg_soft_kernel(SegDemapArgs a) {
                         seg_metrics<6>(cf{v.x, v.y}, hf, p0, p1);                             // symbol 2*lane of the tile
                         seg_metrics<6>(cf{v.z, v.w}, hf, r0, r1);                             // symbol 2*lane + 1
                         // one array at a time through the wave's 3 KB: 12 floats per lane in, 3 x 16 B per lane out
-                        auto emit = [&](float* out, const float (&x)[6], const float (&y)[6]) {
-                            float4* wr = reinterpret_cast<float4*>(st + lane * 12);
-                            wr[0] = float4{x[0], x[1], x[2], x[3]};
-                            wr[1] = float4{x[4], x[5], y[0], y[1]};
-                            wr[2] = float4{y[2], y[3], y[4], y[5]};
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // wave-local exchange: in order per wave
-#pragma unroll
-                            for (int k = 0; k < 3; ++k) {
-                                const int piece = k * 64 + lane;
-                                store_stream16(out + int64_t(t) * (TILE * 6) + 4 * piece, *reinterpret_cast<const float4*>(st + 4 * piece));
-                            }
-                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // reads done before the stage is rewritten
-                        };
-                        if constexpr (S0) emit(q0, p0, r0);
-                        if constexpr (S1) emit(q1, p1, r1);
+                        if constexpr (S0) store_tile64(q0, t, lane, st, p0, r0);
+                        if constexpr (S1) store_tile64(q1, t, lane, st, p1, r1);
                         if constexpr (LL) {
                             float dp[6], dr[6];
 #pragma unroll
@@ -499,7 +462,7 @@ __global__ void __launch_bounds__(256) demap_seg_soft_kernel(SegDemapArgs a) {
                                 dp[b] = p0[b] - p1[b];
                                 dr[b] = r0[b] - r1[b];
                             }
-                            emit(ql, dp, dr);
+                            store_tile64(ql, t, lane, st, dp, dr);
                         }
                     }
                 }

@@ -8,69 +8,15 @@
 //   mrc_llr_kernel     per output symbol: the B matched-filter terms added in branch order, two divisions, the axis rule of the
 //                      channel-state-weighted LLRs, stores as csi_llr_kernel's
 // Every float32 product, sum and quotient below is rounded on its own (contraction off), so the outputs are those of the NumPy
-// restatement in tests/mrc_ref.py bit for bit and do not depend on the path a symbol takes.  The device helpers repeat those of
-// rx_csi.hip (that file is left as it is: its kernels' code does not change).
+// restatement in tests/mrc_ref.py bit for bit and do not depend on the path a symbol takes.  The finite test, the streaming loads
+// and stores, the row wrap and the axis rule are those of soft_device.hpp, shared with rx_csi.hip and rx_demap.hip; the 64-QAM
+// tile store is this kernel's own copy of that header's store_tile64 (see there).
 #include "ofdm_launch.hpp"
+#include "soft_device.hpp"
 
 namespace ofdm {
 
 namespace {
-
-__device__ __forceinline__ bool mrc_finite(float x) { return fabsf(x) < __builtin_inff(); }
-
-__device__ __forceinline__ float4 mrc_load16(const float* p) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-    return float4{v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void mrc_store16(float* p, float4 v) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f4{v.x, v.y, v.z, v.w}, reinterpret_cast<f4*>(p));
-}
-__device__ __forceinline__ float2 mrc_load8(const float* p) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    const f2 v = __builtin_nontemporal_load(reinterpret_cast<const f2*>(p));
-    return float2{v.x, v.y};
-}
-__device__ __forceinline__ void mrc_store8(float* p, float2 v) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    __builtin_nontemporal_store(f2{v.x, v.y}, reinterpret_cast<f2*>(p));
-}
-
-// One axis, as csi_axis of rx_csi.hip: d[j] = min over the levels with axis bit j = 1 of (x-l)^2 minus the same over bit j = 0.
-// Levels and labels are those of rx_demap.hip: +-0.70710678 for QPSK (bit 0 <-> the positive level), else
-// l_q = float(2q - (M-1)) * u with the TS 36.211 7.1 labels.
-template <int MOD>
-__device__ __forceinline__ void mrc_axis(float x, float (&d)[MOD / 2]) {
-#pragma clang fp contract(off)
-    if constexpr (MOD == 2) {
-        constexpr float c = 0.70710678118654752f;
-        const float p = (x - c) * (x - c), n = (x - (-c)) * (x - (-c));
-        d[0] = n - p;
-    } else {
-        constexpr int M = MOD == 4 ? 4 : 8, NB = MOD / 2;
-        const float u = MOD == 4 ? 0.31622776601683794f : 0.15430334996209191f;
-        float m0[NB], m1[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) m0[j] = m1[j] = __builtin_inff();
-#pragma unroll
-        for (int q = 0; q < M; ++q) {
-            const int lv = 2 * q - (M - 1), am = lv < 0 ? -lv : lv;
-            const float l = float(lv) * u;
-            const float e = (x - l) * (x - l);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const bool one = j == 0 ? lv < 0 : (MOD == 4 ? am == 3 : (j == 1 ? am > 4 : (am == 1 || am == 7)));
-                if (one)
-                    m1[j] = fminf(m1[j], e);
-                else
-                    m0[j] = fminf(m0[j], e);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) d[j] = m1[j] - m0[j];
-    }
-}
 
 // The sums of one output symbol: N = sum p, A = sum t over the branches that take part, from +0 in branch order.
 struct MrcAcc {
@@ -81,7 +27,7 @@ struct MrcAcc {
 __device__ __forceinline__ void mrc_add(MrcAcc& s, cf z, float2 t) {
 #pragma clang fp contract(off)
     const float pr = z.x * t.x, pi = z.y * t.x;
-    const bool in = t.x != 0.f && mrc_finite(z.x) && mrc_finite(z.y) && (z.x != 0.f || z.y != 0.f) && mrc_finite(pr) && mrc_finite(pi);
+    const bool in = t.x != 0.f && soft_finite(z.x) && soft_finite(z.y) && (z.x != 0.f || z.y != 0.f) && soft_finite(pr) && soft_finite(pi);
     const float nr = s.nr + pr, ni = s.ni + pi, a = s.a + t.y;
     s.nr = in ? nr : s.nr;
     s.ni = in ? ni : s.ni;
@@ -94,21 +40,19 @@ template <int MOD>
 __device__ __forceinline__ void mrc_finish(MrcAcc s, float (&o)[MOD], cf& u, float& w) {
 #pragma clang fp contract(off)
     const float ur = s.nr / s.a, ui = s.ni / s.a;
-    const bool ok = mrc_finite(s.a) && s.a > 0.f && mrc_finite(ur) && mrc_finite(ui);
-    float dr[MOD / 2], di[MOD / 2];
-    mrc_axis<MOD>(ur, dr);
-    mrc_axis<MOD>(ui, di);
+    const bool ok = soft_finite(s.a) && s.a > 0.f && soft_finite(ur) && soft_finite(ui);
+    float dr[MOD / 2], di[MOD / 2], unused;                                               // the smallest distance is not needed here
+    soft_axis<MOD>(ur, dr, unused);
+    soft_axis<MOD>(ui, di, unused);
 #pragma unroll
     for (int j = 0; j < MOD / 2; ++j) {
         const float vr = s.a * dr[j], vi = s.a * di[j];
-        o[2 * j] = (ok && mrc_finite(vr)) ? vr : 0.f;
-        o[2 * j + 1] = (ok && mrc_finite(vi)) ? vi : 0.f;
+        o[2 * j] = (ok && soft_finite(vr)) ? vr : 0.f;
+        o[2 * j + 1] = (ok && soft_finite(vi)) ? vi : 0.f;
     }
     u = ok ? cf{ur, ui} : cf{0.f, 0.f};
     w = ok ? s.a : 0.f;
 }
-
-__device__ __forceinline__ int mrc_wrap(int j, int rl) { return j >= rl ? j - rl : j; }
 
 // The branch loop is a runtime loop in rounds of MRC_ROUND branches: a lane issues the symbol loads and the table entries of a
 // whole round before any arithmetic (B <= 2: all of them), which bounds the registers the loads hold whatever B is.  Rounds of 4
@@ -131,7 +75,7 @@ __global__ void __launch_bounds__(256) mrc_table_kernel(MrcArgs a) {
         const float w_den = float(var);
         const float av = a.csi[g * a.csi_stride + j];
         const float c = (av + a.rho) / w_den, t = av / w_den;
-        const bool ok = mrc_finite(av) && av > 0.f && mrc_finite(w_den) && w_den > 0.f && mrc_finite(c) && mrc_finite(t) && t > 0.f;
+        const bool ok = soft_finite(av) && av > 0.f && soft_finite(w_den) && w_den > 0.f && soft_finite(c) && soft_finite(t) && t > 0.f;
         a.tab[i] = ok ? float2{c, t} : float2{0.f, 0.f};
         if (j == 0 && a.sigma2_out) a.sigma2_out[g] = var;
     }
@@ -175,7 +119,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                 done = len & ~1;
                 int j = int((j0 + 2u * threadIdx.x) % unsigned(rl));
                 for (int g = threadIdx.x; 2 * g < done; g += 256) {
-                    const int j1 = mrc_wrap(j + 1, rl);
+                    const int j1 = row_wrap(j + 1, rl);
                     MrcAcc s0{0.f, 0.f, 0.f}, s1{0.f, 0.f, 0.f};
                     for (int b0 = 0; b0 < B; b0 += MRC_ROUND) {
                         float4 v[MRC_ROUND];
@@ -185,7 +129,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                             v[k] = float4{0.f, 0.f, 0.f, 0.f};
                             t0[k] = t1[k] = float2{0.f, 0.f};
                             if (b0 + k < B) {
-                                v[k] = mrc_load16(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 4u * unsigned(g));
+                                v[k] = load_stream16(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 4u * unsigned(g));
                                 t0[k] = (tab + (b0 + k) * tb)[unsigned(j)];
                                 t1[k] = (tab + (b0 + k) * tb)[unsigned(j1)];
                             }
@@ -200,10 +144,10 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                     cf u0, u1;
                     mrc_finish<2>(s0, x, u0, w0);
                     mrc_finish<2>(s1, y, u1, w1);
-                    if (ql) mrc_store16(ql + 4 * g, float4{x[0], x[1], y[0], y[1]});
-                    if (qs) mrc_store16(reinterpret_cast<float*>(qs + 2 * g), float4{u0.x, u0.y, u1.x, u1.y});
-                    if (qw) mrc_store8(qw + 2 * g, float2{w0, w1});
-                    j = mrc_wrap(j + step512, rl);
+                    if (ql) store_stream16(ql + 4 * g, float4{x[0], x[1], y[0], y[1]});
+                    if (qs) store_stream16(reinterpret_cast<float*>(qs + 2 * g), float4{u0.x, u0.y, u1.x, u1.y});
+                    if (qw) store_stream8(qw + 2 * g, float2{w0, w1});
+                    j = row_wrap(j + step512, rl);
                 }
             }
         } else if constexpr (MOD == 4) {
@@ -218,7 +162,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                         for (int k = 0; k < MRC_ROUND; ++k) {
                             v[k] = t0[k] = float2{0.f, 0.f};
                             if (b0 + k < B) {
-                                v[k] = mrc_load8(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 2u * unsigned(i));
+                                v[k] = load_stream8(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 2u * unsigned(i));
                                 t0[k] = (tab + (b0 + k) * tb)[unsigned(j)];
                             }
                         }
@@ -228,10 +172,10 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                     float o[4], w0;
                     cf u0;
                     mrc_finish<4>(s0, o, u0, w0);
-                    if (ql) mrc_store16(ql + 4 * i, float4{o[0], o[1], o[2], o[3]});
-                    if (qs) mrc_store8(reinterpret_cast<float*>(qs + i), float2{u0.x, u0.y});
+                    if (ql) store_stream16(ql + 4 * i, float4{o[0], o[1], o[2], o[3]});
+                    if (qs) store_stream8(reinterpret_cast<float*>(qs + i), float2{u0.x, u0.y});
                     if (qw) __builtin_nontemporal_store(w0, qw + i);
-                    j = mrc_wrap(j + step256, rl);
+                    j = row_wrap(j + step256, rl);
                 }
             }
         } else {
@@ -242,7 +186,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                 float* st = stage[wave];
                 int j = int((j0 + unsigned(wave * TILE + 2 * lane)) % unsigned(rl));
                 for (int t = wave; t < n_tiles; t += 4) {
-                    const int j1 = mrc_wrap(j + 1, rl), i0 = t * TILE + 2 * lane;
+                    const int j1 = row_wrap(j + 1, rl), i0 = t * TILE + 2 * lane;
                     MrcAcc s0{0.f, 0.f, 0.f}, s1{0.f, 0.f, 0.f};
                     for (int b0 = 0; b0 < B; b0 += MRC_ROUND) {
                         float4 v[MRC_ROUND];
@@ -252,7 +196,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                             v[k] = float4{0.f, 0.f, 0.f, 0.f};
                             t0[k] = t1[k] = float2{0.f, 0.f};
                             if (b0 + k < B) {
-                                v[k] = mrc_load16(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 2u * unsigned(i0));
+                                v[k] = load_stream16(reinterpret_cast<const float*>(p + (b0 + k) * zb) + 2u * unsigned(i0));
                                 t0[k] = (tab + (b0 + k) * tb)[unsigned(j)];
                                 t1[k] = (tab + (b0 + k) * tb)[unsigned(j1)];
                             }
@@ -267,10 +211,12 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                     cf u0, u1;
                     mrc_finish<6>(s0, x, u0, w0);                                         // symbol 2*lane of the tile
                     mrc_finish<6>(s1, y, u1, w1);                                         // symbol 2*lane + 1
-                    if (qs) mrc_store16(reinterpret_cast<float*>(qs + i0), float4{u0.x, u0.y, u1.x, u1.y});
-                    if (qw) mrc_store8(qw + i0, float2{w0, w1});
+                    if (qs) store_stream16(reinterpret_cast<float*>(qs + i0), float4{u0.x, u0.y, u1.x, u1.y});
+                    if (qw) store_stream8(qw + i0, float2{w0, w1});
                     if (ql) {
-                        // through the wave's 3 KB: 12 floats per lane in, 3 x 16 B per lane out
+                        // store_tile64 of soft_device.hpp written out: through it this kernel's prologue came out in another order,
+                        // and the timing against the parent's library did not hold its bound (profiles/soft_stage_header_ab.txt).
+                        // Through the wave's 3 KB: 12 floats per lane in, 3 x 16 B per lane out.
                         float4* wr = reinterpret_cast<float4*>(st + lane * 12);
                         wr[0] = float4{x[0], x[1], x[2], x[3]};
                         wr[1] = float4{x[4], x[5], y[0], y[1]};
@@ -279,11 +225,11 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
                             const int piece = k * 64 + lane;
-                            mrc_store16(ql + int64_t(t) * (TILE * 6) + 4 * piece, *reinterpret_cast<const float4*>(st + 4 * piece));
+                            store_stream16(ql + int64_t(t) * (TILE * 6) + 4 * piece, *reinterpret_cast<const float4*>(st + 4 * piece));
                         }
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // reads done before the stage is rewritten
                     }
-                    j = mrc_wrap(j + step512, rl);
+                    j = row_wrap(j + step512, rl);
                 }
             }
         }
@@ -318,7 +264,7 @@ __global__ void __launch_bounds__(256) mrc_llr_kernel(MrcArgs a) {
                     reinterpret_cast<float*>(qs + i)[1] = u0.y;
                 }
                 if (qw) qw[i] = w0;
-                j = mrc_wrap(j + step256, rl);
+                j = row_wrap(j + step256, rl);
             }
         }
     }

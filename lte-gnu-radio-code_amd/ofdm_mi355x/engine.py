@@ -34,6 +34,42 @@ def _mod_bits(modulation) -> int:
     return int(modulation)
 
 
+def _addr(x):
+    """Address of a buffer as an int (None stays None): the pointer fields of the *Out structures."""
+    p = ptr(x)
+    return None if p is None else p.value
+
+
+def _work(fn, handle, report, in0: np.ndarray, out: np.ndarray) -> int:
+    """One work() call of a stream block (fn = ofdm_rx_work / ofdm_fo_work): raw status; `out` is written through a
+    contiguous complex64 copy where it is not one itself."""
+    in0 = np.ascontiguousarray(in0, dtype=np.complex64)
+    if out.dtype != np.complex64 or not out.flags.c_contiguous:
+        tmp = np.ascontiguousarray(out, dtype=np.complex64)
+        rc = fn(handle, ptr(in0), in0.size, ptr(tmp), tmp.size, C.byref(report))
+        if rc >= 0:
+            out[...] = tmp
+        return int(rc)
+    return int(fn(handle, ptr(in0), in0.size, ptr(out), out.size, C.byref(report)))
+
+
+class _Handle:
+    """What the four engines share: the library handle `_h`, destroyed once by the library function named in `_destroy`
+    (close(), or when the object is collected)."""
+    _destroy = ""
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self.lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceBuffer:
     """Plain HBM allocation through the C ABI (for hosts that do not use torch)."""
 
@@ -163,8 +199,9 @@ def gold_bits(c_init: int, first: int, n: int) -> np.ndarray:
     return out
 
 
-class RxEngine:
+class RxEngine(_Handle):
     """Receive chain handle (sync search, LS channel estimate, FFT + equalise, de-map)."""
+    _destroy = "ofdm_rx_destroy"
 
     def __init__(self, num_ofdm_symb, nfft, cp_len, num_synch_bins, synch_dat, num_data_bins, snr,
                  scale_factor_gate=0.7, compat=_lib.COMPAT_UTSA, modulation="QPSK", device=0):
@@ -181,14 +218,7 @@ class RxEngine:
     def work(self, in0: np.ndarray, out: np.ndarray) -> int:
         """Returns the raw status; the caller copies `self.report` (valid even when the reference would have
         raised after its sync search) and then passes the status to `_lib.check`."""
-        in0 = np.ascontiguousarray(in0, dtype=np.complex64)
-        if out.dtype != np.complex64 or not out.flags.c_contiguous:
-            tmp = np.ascontiguousarray(out, dtype=np.complex64)
-            rc = self.lib.ofdm_rx_work(self._h, ptr(in0), in0.size, ptr(tmp), tmp.size, C.byref(self.report))
-            if rc >= 0:
-                out[...] = tmp
-            return int(rc)
-        return int(self.lib.ofdm_rx_work(self._h, ptr(in0), in0.size, ptr(out), out.size, C.byref(self.report)))
+        return _work(self.lib.ofdm_rx_work, self._h, self.report, in0, out)
 
     def state(self, row: int = 0):
         c = self.cfg
@@ -246,10 +276,7 @@ class RxEngine:
     # ---- segmented soft de-mapper: one sigma per segment (per frame of a batch) ----------------------------------
     @staticmethod
     def _soft_out(d_soft0, d_soft1, d_llr, d_sigma):
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        return _lib.SoftOut(addr(d_soft0), addr(d_soft1), addr(d_llr), addr(d_sigma))
+        return _lib.SoftOut(_addr(d_soft0), _addr(d_soft1), _addr(d_llr), _addr(d_sigma))
 
     def reserve_soft(self, n_seg: int, seg_len: int):
         """Workspace of demap_frames / demod_frames_soft for n_seg segments of seg_len symbols (before a graph capture)."""
@@ -282,10 +309,7 @@ class RxEngine:
 
     @staticmethod
     def _pilot_out(d_data, d_bits, bits_mode, d_cpe, d_slope, d_cfo):
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        return _lib.PilotOut(addr(d_data), addr(d_bits), int(bits_mode), addr(d_cpe), addr(d_slope), addr(d_cfo))
+        return _lib.PilotOut(_addr(d_data), _addr(d_bits), int(bits_mode), _addr(d_cpe), _addr(d_slope), _addr(d_cfo))
 
     def reserve_pilots(self, n_seg: int, rows: int):
         """Workspace of the cfo output for n_seg segments of `rows` rows (before a graph capture)."""
@@ -313,10 +337,7 @@ class RxEngine:
     # ---- channel-state-weighted LLRs: every symbol weighed with |H|^2 of its bin (include/ofdm_mi355x.h) ---------------------
     @staticmethod
     def _csi_out(d_llr, d_sigma2, d_n_used):
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        return _lib.CsiOut(addr(d_llr), addr(d_sigma2), addr(d_n_used))
+        return _lib.CsiOut(_addr(d_llr), _addr(d_sigma2), _addr(d_n_used))
 
     @property
     def csi_rho(self) -> float:
@@ -359,10 +380,7 @@ class RxEngine:
     # ---- receive-diversity combining: B branches added with maximum-ratio weights, LLRs of the sum (include/ofdm_mi355x.h) ------
     @staticmethod
     def _mrc_out(d_llr, d_sym_out, d_weight):
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        return _lib.MrcOut(addr(d_llr), addr(d_sym_out), addr(d_weight))
+        return _lib.MrcOut(_addr(d_llr), _addr(d_sym_out), _addr(d_weight))
 
     @staticmethod
     def _mrc_noise(noise_var, n_branch):
@@ -416,10 +434,7 @@ class RxEngine:
                            d_tb_ok=None, stream=None):
         """ofdm_tbcc_decode_frames: block (s, b) = the 3K float32 LLRs at d_llr + s*seg_stride + b*3K (seg_stride in floats).
         Outputs dense per block: bits [K] (one per byte, or packed MSB-first), metric float32, tb_ok int32."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
+        out = _lib.TbccOut(_addr(d_bits), int(bits_mode), _addr(d_metric), _addr(d_tb_ok))
         check(self.lib.ofdm_tbcc_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                C.byref(out), ptr(stream)))
 
@@ -434,10 +449,7 @@ class RxEngine:
                               d_metric=None, d_tb_ok=None, stream=None):
         """ofdm_tbcc_decode_rm_frames: tbcc_decode_frames on rate-matched LLRs (block (s, b) = E floats at d_llr + s*seg_stride +
         b*E), de-matched inside the decoder's launch.  reserve_tbcc prepares this call too."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TbccOut(addr(d_bits), int(bits_mode), addr(d_metric), addr(d_tb_ok))
+        out = _lib.TbccOut(_addr(d_bits), int(bits_mode), _addr(d_metric), _addr(d_tb_ok))
         check(self.lib.ofdm_tbcc_decode_rm_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                   int(E), C.byref(out), ptr(stream)))
 
@@ -451,10 +463,7 @@ class RxEngine:
         """ofdm_turbo_decode_frames: block (s, b) = the 3K + 12 float32 LLRs at d_llr + s*seg_stride + b*(3K + 12) (seg_stride in
         floats), QPP interleaver (f1, f2), n_iter iterations.  Outputs dense per block: bits [K] (one per byte, or packed
         MSB-first), a-posteriori llr [K] float32."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TurboOut(addr(d_bits), int(bits_mode), addr(d_llr_out))
+        out = _lib.TurboOut(_addr(d_bits), int(bits_mode), _addr(d_llr_out))
         check(self.lib.ofdm_turbo_decode_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                 int(f1), int(f2), int(n_iter), C.byref(out), ptr(stream)))
 
@@ -468,10 +477,7 @@ class RxEngine:
         first iteration whose hard decisions are divisible by the generator of crc_kind (all K bits, zero mask), at max_iter
         otherwise; its bits and llr are those of turbo_decode_frames at that n_iter.  iters / crc_ok: uint8 per block at
         s*stat_stride + b (0 = blocks_per_seg)."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TurboEsOut(addr(d_bits), int(bits_mode), addr(d_llr_out), addr(d_iters), addr(d_crc_ok), int(stat_stride))
+        out = _lib.TurboEsOut(_addr(d_bits), int(bits_mode), _addr(d_llr_out), _addr(d_iters), _addr(d_crc_ok), int(stat_stride))
         check(self.lib.ofdm_turbo_decode_es_frames(self._h, ptr(d_llr), int(n_seg), int(seg_stride), int(blocks_per_seg), int(K),
                                                    int(f1), int(f2), int(crc_kind), int(min_iter), int(max_iter), C.byref(out),
                                                    ptr(stream)))
@@ -501,10 +507,7 @@ class RxEngine:
         """ofdm_tb_decode_frames: the G LLRs of transport block t at d_llr + t*llr_stride -> its HARQ soft buffer at
         d_soft + t*soft_stride (written, or added to with accumulate) -> payload [n_tb][A], tb_ok [n_tb], cb_ok [n_tb][C],
         syndrome [n_tb] (each only where given).  qpp_plus / qpp_minus: (f1, f2) for K+ and K- of tb_geometry(A, Z)."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TbOut(addr(d_payload), int(payload_mode), addr(d_tb_ok), addr(d_cb_ok), addr(d_syndrome))
+        out = _lib.TbOut(_addr(d_payload), int(payload_mode), _addr(d_tb_ok), _addr(d_cb_ok), _addr(d_syndrome))
         check(self.lib.ofdm_tb_decode_frames(self._h, ptr(d_llr), int(n_tb), int(llr_stride), int(A), int(Z), int(G), int(q), int(N_IR),
                                              int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]), int(rv), ptr(d_rv),
                                              int(n_iter), int(bool(accumulate)), ptr(d_soft), int(soft_stride), C.byref(out), ptr(stream)))
@@ -518,10 +521,7 @@ class RxEngine:
                             d_tb_ok=None, d_cb_ok=None, d_syndrome=None, d_cb_iters=None, stream=None):
         """ofdm_tb_decode_es_frames: tb_decode_frames with every code block stopped at its first passing CRC (CRC24B, or the
         transport block's CRC24A when C = 1) between min_iter and max_iter; cb_iters [n_tb][C] uint8 = the iterations it ran."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.TbEsOut(addr(d_payload), int(payload_mode), addr(d_tb_ok), addr(d_cb_ok), addr(d_syndrome), addr(d_cb_iters))
+        out = _lib.TbEsOut(_addr(d_payload), int(payload_mode), _addr(d_tb_ok), _addr(d_cb_ok), _addr(d_syndrome), _addr(d_cb_iters))
         check(self.lib.ofdm_tb_decode_es_frames(self._h, ptr(d_llr), int(n_tb), int(llr_stride), int(A), int(Z), int(G), int(q),
                                                 int(N_IR), int(qpp_minus[0]), int(qpp_minus[1]), int(qpp_plus[0]), int(qpp_plus[1]),
                                                 int(rv), ptr(d_rv), int(min_iter), int(max_iter), int(bool(accumulate)), ptr(d_soft),
@@ -543,28 +543,15 @@ class RxEngine:
         """ofdm_crc_check_frames: d_info dense [n_blocks][A + L] bits as the decoders write them -> ok uint8 (syndrome == mask),
         syndrome uint32 (CRC of the first A bits ^ the received parity), payload dense [n_blocks][A]; mask: the scalar, or
         d_mask one device uint32 per block."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.CrcOut(addr(d_ok), addr(d_syndrome), addr(d_payload), int(payload_mode))
+        out = _lib.CrcOut(_addr(d_ok), _addr(d_syndrome), _addr(d_payload), int(payload_mode))
         check(self.lib.ofdm_crc_check_frames(self._h, ptr(d_info), int(info_mode), int(n_blocks), int(A), int(kind), int(mask),
                                              ptr(d_mask), C.byref(out), ptr(stream)))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.ofdm_rx_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FoEngine:
+class FoEngine(_Handle):
     """CFO-search receiver handle (reference: LEGACY/gr-ofdm-rx/python/SynchEstAndFO.py): trial x candidate sync table,
     up to 100 syncs per call, one equalised data symbol per sync."""
+    _destroy = "ofdm_fo_destroy"
 
     def __init__(self, num_ofdm_symb, nfft, cp_len, num_synch_bins, synch_dat, num_data_bins, snr, rotators, device=0,
                  spread_code=None):
@@ -590,14 +577,7 @@ class FoEngine:
 
     def work(self, in0: np.ndarray, out: np.ndarray) -> int:
         """Raw status (see RxEngine.work)."""
-        in0 = np.ascontiguousarray(in0, dtype=np.complex64)
-        if out.dtype != np.complex64 or not out.flags.c_contiguous:
-            tmp = np.ascontiguousarray(out, dtype=np.complex64)
-            rc = self.lib.ofdm_fo_work(self._h, ptr(in0), in0.size, ptr(tmp), tmp.size, C.byref(self.report))
-            if rc >= 0:
-                out[...] = tmp
-            return int(rc)
-        return int(self.lib.ofdm_fo_work(self._h, ptr(in0), in0.size, ptr(out), out.size, C.byref(self.report)))
+        return _work(self.lib.ofdm_fo_work, self._h, self.report, in0, out)
 
     def state(self):
         c = self.cfg
@@ -627,30 +607,17 @@ class FoEngine:
         """ofdm_fo_demod_frames on device buffers; returns the rows per frame (FO_MAX_SYNC).  Per frame: status = n_sync or
         OFDM_ERR_INDEX (a 101st sync), tsr [100][3] int32, fo_idx int32, data_freq [100][Kd] complex64, bits, data_freq_d
         [100][Kd/DSSS], chan_freq / chan_time [100][nfft], synch_freq [100][S*Ks]; rows >= n_sync are zero."""
-        def addr(x):
-            p = ptr(x)
-            return None if p is None else p.value
-        out = _lib.FoBatchOut(addr(d_status), addr(d_tsr), addr(d_fo_idx), addr(d_data_freq), addr(d_bits), int(bits_mode),
-                              addr(d_data_freq_d), addr(d_chan_freq), addr(d_chan_time), addr(d_synch_freq))
+        out = _lib.FoBatchOut(_addr(d_status), _addr(d_tsr), _addr(d_fo_idx), _addr(d_data_freq), _addr(d_bits), int(bits_mode),
+                              _addr(d_data_freq_d), _addr(d_chan_freq), _addr(d_chan_time), _addr(d_synch_freq))
         return int(check(self.lib.ofdm_fo_demod_frames(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
                                                        C.byref(out), ptr(stream))))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.ofdm_fo_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TrkEngine:
+class TrkEngine(_Handle):
     """Device primitives of the regression-tracking receiver (reference: LEGACY/gr-ofdm-rx/python/SynchronizeAndEstimate.py):
     strided / single sync trials, LS estimate per accepted sync, data stage.  The sequential pointer logic lives in the
     block mirror (`blocks.SynchronizeAndEstimate`)."""
+    _destroy = "ofdm_trk_destroy"
 
     def __init__(self, nfft, cp_len, num_synch_bins, num_data_bins, synch_D, rows_sync, rows_data, snr, zc_root=23, device=0):
         self.lib = _lib.load()
@@ -691,20 +658,10 @@ class TrkEngine:
         check(self.lib.ofdm_trk_get_state(self._h, ptr(H), ptr(imp), ptr(esf), ptr(edf) if c.rows_data > 0 else None))
         return dict(chan_freq=H, chan_impulse=imp, synch_freq=esf, data_freq=edf)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.ofdm_trk_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TxEngine:
+class TxEngine(_Handle):
     """Transmit chain handle (bit map, resource grid + ZC sync symbols, IFFT + CP + normalise) and channel."""
+    _destroy = "ofdm_tx_destroy"
 
     def __init__(self, nfft, cp_len, num_synch_bins, num_data_bins, synch_dat=(1, 3), modulation="QPSK",
                  zc_root=23, device=0):
@@ -835,14 +792,3 @@ class TxEngine:
         check(self.lib.ofdm_channel_apply(self._h, ptr(d_in), int(n_frames), int(in_stride), int(in_len), ptr(d_taps),
                                           int(n_taps), int(bool(per_frame_taps)), float(noise_var), int(seed),
                                           ptr(d_out), int(out_stride), int(out_len), ptr(stream)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.ofdm_tx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
