@@ -283,16 +283,8 @@ hipError_t launch_crc(const CrcArgs& a, hipStream_t s) {
 }
 
 hipError_t bitproc_prepare() {
-    hipFuncAttributes fa;
-    const void* fns[] = {reinterpret_cast<const void*>(gold_apply_kernel<GOLD_MODE_LLR>),
-                         reinterpret_cast<const void*>(gold_apply_kernel<GOLD_MODE_BYTES>),
-                         reinterpret_cast<const void*>(gold_apply_kernel<GOLD_MODE_PACKED>),
-                         reinterpret_cast<const void*>(crc_kernel<true>), reinterpret_cast<const void*>(crc_kernel<false>)};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncGetAttributes(&fa, f);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return load_kernels(gold_apply_kernel<GOLD_MODE_LLR>, gold_apply_kernel<GOLD_MODE_BYTES>, gold_apply_kernel<GOLD_MODE_PACKED>,
+                        crc_kernel<true>, crc_kernel<false>);
 }
 
 }  // namespace ofdm

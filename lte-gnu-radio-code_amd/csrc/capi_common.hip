@@ -1,5 +1,5 @@
 // capi_common.hip -- what belongs to no handle: the error text, the host-built tables (twiddles, Zadoff-Chu, scan kernel),
-// the derived receiver constants, and the handle-free calls (device memory, sharding, probe, bit-error count, TBCC block counts, host CRC and Gold sequence).
+// the derived receiver constants, and the handle-free calls (device memory, sharding, probe, bit-error count).
 #include "capi_internal.hpp"
 
 static thread_local std::string g_last_error;
@@ -180,41 +180,6 @@ int ofdm_count_bit_errors(int32_t device, const uint8_t* d_a, const uint8_t* d_b
     if (n_bytes > (int64_t(1) << 40)) return fail(OFDM_ERR_INVALID, "ofdm_count_bit_errors: more than 2^40 bytes per call");
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(launch_bit_errors(d_a, d_b, n_bytes, reinterpret_cast<unsigned long long*>(d_count), static_cast<hipStream_t>(stream)));
-    return OFDM_OK;
-}
-
-int64_t ofdm_tbcc_blocks(int64_t seg_bits, int32_t K) {
-    if (!tbcc_valid_k(K)) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_blocks: K must be a multiple of 8 with 24 <= K <= 2048");
-    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_blocks: negative seg_bits");
-    return seg_bits / (3 * int64_t(K));
-}
-
-int64_t ofdm_tbcc_rm_blocks(int64_t seg_bits, int32_t K, int32_t E) {
-    const char* bad = tbcc_rm_bad_geometry(0, 0, K, E);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rm_blocks: %s", bad);
-    if (seg_bits < 0) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rm_blocks: negative seg_bits");
-    return seg_bits / E;
-}
-
-int32_t ofdm_crc_bits(int32_t kind) {
-    if (kind < OFDM_CRC24A || kind > OFDM_CRC8) return fail(OFDM_ERR_INVALID, "ofdm_crc_bits: unknown kind %d", int(kind));
-    return crc_bits(kind);
-}
-
-int ofdm_crc_compute(int32_t kind, const uint8_t* host_bits_packed, int32_t A, uint32_t* crc) {
-    const char* bad = crc_bad_geometry(kind, A);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_crc_compute: %s", bad);
-    if (!host_bits_packed || !crc) return fail(OFDM_ERR_INVALID, "ofdm_crc_compute: null argument");
-    *crc = crc_host(kind, host_bits_packed, A);
-    return OFDM_OK;
-}
-
-int ofdm_gold_bits(uint32_t c_init, int64_t first, int64_t n, uint8_t* host_out) {
-    if (first < 0 || n < 0) return fail(OFDM_ERR_INVALID, "ofdm_gold_bits: negative count");
-    if (first > GOLD_MAX_BITS || n > GOLD_MAX_BITS - first) return fail(OFDM_ERR_INVALID, "ofdm_gold_bits: first + n beyond 2^31 - 1600");
-    if (n == 0) return OFDM_OK;
-    if (!host_out) return fail(OFDM_ERR_INVALID, "ofdm_gold_bits: null host_out");
-    gold_bits_host(c_init, first, n, host_out);
     return OFDM_OK;
 }
 

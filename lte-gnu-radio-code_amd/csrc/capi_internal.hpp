@@ -378,49 +378,62 @@ int check_pattern(int S, int D, int num_ofdm_symb) {
     return OFDM_OK;
 }
 
-// ---- TBCC argument checks shared by the encoders (capi_tx.hip) and the decoders (capi_rx_stages.hip); "" = fine
-constexpr int64_t TBCC_MAX_BLOCKS = (int64_t(1) << 31) - 1;   // one workgroup per block: the grid's x range
-constexpr int64_t TBCC_MAX_ITEMS = int64_t(1) << 40;          // n_seg * seg_stride (floats) and n_seg * seg_bits
-bool tbcc_bits_mode_ok(int32_t m) { return m == OFDM_BITS_PACKED || m == OFDM_BITS_UNPACKED; }
-bool tbcc_items_ok(int64_t n_seg, int64_t per_seg) { return per_seg <= TBCC_MAX_ITEMS && (n_seg <= 0 || per_seg <= TBCC_MAX_ITEMS / n_seg); }
-const char* tbcc_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K) {
-    if (!tbcc_valid_k(K)) return "K must be a multiple of 8 with 24 <= K <= 2048";
-    if (n_seg < 0 || blocks_per_seg < 0) return "negative count";
-    if (blocks_per_seg > TBCC_MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS / blocks_per_seg))
-        return "batch beyond the kernels' index range";
+// ---- what the batch calls of the codecs share (capi_tbcc.hip, capi_turbo.hip, capi_bitproc.hip, capi_tb.hip); "" = fine
+constexpr int64_t MAX_BLOCKS = (int64_t(1) << 31) - 1;        // one workgroup per block: the grid's x range
+constexpr int64_t MAX_ITEMS = int64_t(1) << 40;               // n_seg * seg_stride (floats) and n_seg * seg_bits
+bool bits_mode_ok(int32_t m) { return m == OFDM_BITS_PACKED || m == OFDM_BITS_UNPACKED; }
+bool batch_items_ok(int64_t n_seg, int64_t per_seg) { return per_seg <= MAX_ITEMS && (n_seg <= 0 || per_seg <= MAX_ITEMS / n_seg); }
+// what an encode checks after its geometry: `need` coded bits per segment, `short_text` the text for a shorter segment
+const char* enc_bad_args(int32_t info_mode, int32_t coded_mode, int64_t n_seg, int64_t seg_bits, int64_t need, const char* short_text) {
+    if (!bits_mode_ok(info_mode) || !bits_mode_ok(coded_mode)) return "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+    if (seg_bits < 0 || seg_bits < need) return short_text;
+    if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) return "packed coded bits need seg_bits % 8 == 0";
+    if (!batch_items_ok(n_seg, seg_bits)) return "batch beyond the kernel's index range";
     return "";
 }
-// the same with rate matching (TS 36.212 5.1.4.2): E coded bits per block
-const char* tbcc_rm_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K, int64_t E) {
-    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
-    if (*bad) return bad;
-    if (!tbcc_valid_e(K, E)) return "E must lie in 1 .. 48K";
+// what a decode checks after its geometry: `need` LLRs per segment, `short_text` the text for a shorter stride
+template <class Out>
+const char* dec_bad_args(int64_t n_seg, int64_t seg_stride, int64_t need, const char* short_text, const Out* out) {
+    if (seg_stride < need) return short_text;
+    if (!batch_items_ok(n_seg, seg_stride)) return "batch beyond the kernel's index range";
+    if (out && out->bits && !bits_mode_ok(out->bits_mode)) return "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
     return "";
 }
-
-// ---- CRC and scrambling argument checks shared by capi_common.hip, capi_tx.hip and capi_rx_stages.hip; "" = fine
-const char* crc_bad_geometry(int32_t kind, int64_t A) {
-    if (kind < OFDM_CRC24A || kind > OFDM_CRC8) return "kind must be OFDM_CRC24A, OFDM_CRC24B, OFDM_CRC16 or OFDM_CRC8";
-    if (A < CRC_A_MIN || A > CRC_A_MAX || A % 8) return "A must be a multiple of 8 with 8 <= A <= 2040";
-    if (A + crc_bits(kind) > CRC_K_MAX) return "A + L must not exceed 2048";
-    return "";
+// the fields every encoder's and every decoder's argument struct has
+template <class Args>
+void enc_fill(Args& a, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg, uint8_t* d_coded,
+              int32_t coded_mode, int64_t seg_bits) {
+    a.info = d_info;
+    a.info_mode = info_mode;
+    a.n_seg = n_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.coded = d_coded;
+    a.coded_mode = coded_mode;
+    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
 }
-const char* crc_bad_args(int32_t kind, int64_t A, int64_t n_blocks, int32_t mode_a, int32_t mode_b, uint32_t mask, const uint32_t* d_mask) {
-    const char* bad = crc_bad_geometry(kind, A);
-    if (*bad) return bad;
-    if (n_blocks < 0) return "negative count";
-    if (n_blocks > TBCC_MAX_BLOCKS) return "batch beyond the kernel's index range";
-    if (!tbcc_bits_mode_ok(mode_a) || !tbcc_bits_mode_ok(mode_b)) return "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-    if (!d_mask && (mask >> crc_bits(kind))) return "scalar mask has bits at or above L";
-    return "";
+template <class Args, class Out>
+void dec_fill(Args& a, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, const Out* out) {
+    a.llr = d_llr;
+    a.seg_stride = seg_stride;
+    a.n_blocks = n_seg * blocks_per_seg;
+    a.blocks_per_seg = blocks_per_seg;
+    a.bits = out->bits;
+    a.bits_mode = out->bits_mode;
 }
-// n_seg segments of seg_bits scrambled bits at strides of stride_a / stride_b elements
-const char* gold_bad_args(int64_t n_seg, int64_t seg_bits, int64_t stride_a, int64_t stride_b) {
-    if (n_seg < 0 || seg_bits < 0) return "negative count";
-    if (seg_bits >= GOLD_MAX_BITS) return "seg_bits must be below 2^31 - 1600";
-    if (stride_a < seg_bits || stride_b < seg_bits) return "stride shorter than seg_bits";
-    if (!tbcc_items_ok(n_seg, stride_a) || !tbcc_items_ok(n_seg, stride_b)) return "batch beyond the kernel's index range";
-    return "";
+// a reserve call with no workspace: it loads the code objects a first launch inside a capture would otherwise have to
+template <class H>
+int prepare_only(H* h, const char* who, hipError_t (*prepare)()) {
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(prepare());
+    return OFDM_OK;
+}
+// the ensure step of both turbo decoders: the handle's workspace holds `need` floats, or grows through `reserve` -- outside a capture
+int turbo_ensure(ofdm_rx* h, int64_t need, int64_t n_blocks, int32_t K, hipStream_t s, const char* who, const char* reserve_name,
+                 int (*reserve)(ofdm_rx*, int64_t, int32_t)) {
+    if (need <= h->cap_turbo) return OFDM_OK;
+    const int rc = refuse_growth_in_capture(s, who, reserve_name);
+    return rc != OFDM_OK ? rc : reserve(h, n_blocks, K);
 }
 
 }  // namespace

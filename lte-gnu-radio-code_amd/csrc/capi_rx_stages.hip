@@ -1,36 +1,8 @@
-// capi_rx_stages.hip -- the stages that run behind the batch receiver on its handle: segmented soft de-mapper, pilot-aided phase
-// tracking (with ofdm_rx_set_pilots), TBCC decode and rate de-matching, and the calls that chain them to ofdm_rx_demod_frames.
+// capi_rx_stages.hip -- the stages that run behind the batch receiver on its handle: segmented soft de-mapper and pilot-aided
+// phase tracking (with ofdm_rx_set_pilots), and the calls that chain them to ofdm_rx_demod_frames.
 #include "capi_internal.hpp"
 
-// ---- LTE tail-biting convolutional code on the frame-batched path (definition: include/ofdm_mi355x.h): decode
-namespace {
-bool tbcc_wanted(const ofdm_tbcc_out* o) { return o && (o->bits || o->metric || o->tb_ok); }
-// what the two decodes check after their geometry: `need` LLRs per segment (blocks_per_seg * 3K, or * E rate-matched), `short_text`
-// the text for a shorter stride; "" = fine
-const char* tbcc_dec_bad_args(int64_t n_seg, int64_t seg_stride, int64_t need, const char* short_text, const ofdm_tbcc_out* out) {
-    if (seg_stride < need) return short_text;
-    if (!tbcc_items_ok(n_seg, seg_stride)) return "batch beyond the kernel's index range";
-    if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode)) return "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-    return "";
-}
-template <class Args>
-void tbcc_dec_fill(Args& a, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K, const ofdm_tbcc_out* out) {
-    a.llr = d_llr;
-    a.seg_stride = seg_stride;
-    a.n_blocks = n_seg * blocks_per_seg;
-    a.blocks_per_seg = blocks_per_seg;
-    a.K = K;
-    a.bits = out->bits;
-    a.bits_mode = out->bits_mode;
-    a.metric = out->metric;
-    a.tb_ok = out->tb_ok;
-}
-}  // namespace
-
-extern "C" {
-
 // ---- segmented soft de-mapper (one sigma per segment = per frame of the batch path)
-}  // extern "C"
 namespace {
 bool soft_wanted(const ofdm_soft_out* o) { return o && (o->soft0 || o->soft1 || o->llr || o->sigma); }
 // argument check shared by both entry points (no device access); "" = fine
@@ -304,132 +276,6 @@ int64_t ofdm_rx_demod_frames_pilots(ofdm_rx* h, const float* d_iq, int64_t n_fra
     int rc = pilot_launch(h, d_eq, n_frames, n_dsym, n_dsym * d.Kd, d.D, mode, out, s);
     if (rc == OFDM_OK && want_soft && seg_len > 0) rc = soft_launch(h, out->data, n_frames, seg_len, seg_len, h->cfg.modulation, soft, s);
     return rc != OFDM_OK ? rc : r;
-}
-
-// The decoder keeps its survivors in LDS and has no device workspace, so there is nothing to allocate: the call checks the
-// geometry a later decode will use and loads the code objects of both decoders (plain and rate-matched), which is the one piece
-// of set-up a first launch would otherwise do inside a capture.
-int ofdm_rx_reserve_tbcc(ofdm_rx* h, int64_t n_blocks, int32_t K) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tbcc: null handle");
-    const char* bad = tbcc_bad_geometry(1, n_blocks, K);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_tbcc: %s", bad);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(tbcc_decode_prepare());
-    return OFDM_OK;
-}
-
-int ofdm_tbcc_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg, int32_t K,
-                            const ofdm_tbcc_out* out, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: null handle");
-    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
-    if (!*bad) bad = tbcc_dec_bad_args(n_seg, seg_stride, int64_t(blocks_per_seg) * 3 * K, "seg_stride < blocks_per_seg * 3K", out);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: %s", bad);
-    if (n_seg == 0 || blocks_per_seg == 0 || !tbcc_wanted(out)) return OFDM_OK;
-    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_frames: null d_llr");
-    TbccDecArgs a{};
-    tbcc_dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, K, out);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_tbcc_decode(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-int ofdm_tbcc_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
-                                  int32_t K, int32_t E, float* d_out, int64_t out_stride, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: null handle");
-    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: %s", bad);
-    if (seg_stride < int64_t(blocks_per_seg) * E)
-        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: seg_stride < blocks_per_seg * E");
-    if (out_stride < int64_t(blocks_per_seg) * 3 * K)
-        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: out_stride < blocks_per_seg * 3K");
-    // one thread per output LLR in workgroups of 256: the grid's x range bounds n_seg * blocks_per_seg * 3K
-    if (!tbcc_items_ok(n_seg, seg_stride) || !tbcc_items_ok(n_seg, out_stride) ||
-        n_seg * int64_t(blocks_per_seg) > TBCC_MAX_BLOCKS * int64_t(256) / (3 * K))
-        return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: batch beyond the kernel's index range");
-    if (n_seg == 0 || blocks_per_seg == 0) return OFDM_OK;
-    if (!d_llr || !d_out) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_rate_dematch_frames: null buffer");
-    TbccDematchArgs a{};
-    a.llr = d_llr;
-    a.seg_stride = seg_stride;
-    a.n_blocks = n_seg * blocks_per_seg;
-    a.blocks_per_seg = blocks_per_seg;
-    a.K = K;
-    a.out = d_out;
-    a.out_stride = out_stride;
-    a.g = tbcc_rm_geom(K, E);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_tbcc_dematch(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-int ofdm_tbcc_decode_rm_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int32_t blocks_per_seg,
-                               int32_t K, int32_t E, const ofdm_tbcc_out* out, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: null handle");
-    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
-    if (!*bad) bad = tbcc_dec_bad_args(n_seg, seg_stride, int64_t(blocks_per_seg) * E, "seg_stride < blocks_per_seg * E", out);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: %s", bad);
-    if (n_seg == 0 || blocks_per_seg == 0 || !tbcc_wanted(out)) return OFDM_OK;
-    if (!d_llr) return fail(OFDM_ERR_INVALID, "ofdm_tbcc_decode_rm_frames: null d_llr");
-    TbccDecRmArgs a{};
-    tbcc_dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, K, out);
-    a.g = tbcc_rm_geom(K, E);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_tbcc_decode_rm(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-// ---- Gold-sequence descrambling of LLRs and the CRC check (definition: include/ofdm_mi355x.h)
-int ofdm_rx_reserve_bitproc(ofdm_rx* h) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_bitproc: null handle");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(bitproc_prepare());
-    return OFDM_OK;
-}
-
-int ofdm_descramble_llr_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int64_t seg_stride, int64_t seg_bits,
-                               const uint32_t* d_cinit, float* d_out, int64_t out_stride, void* stream) {
-    const char* bad = gold_bad_args(n_seg, seg_bits, seg_stride, out_stride);
-    if (!*bad && d_llr && d_out == d_llr && out_stride != seg_stride) bad = "in place needs out_stride == seg_stride";
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: %s", bad);
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: null handle");
-    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
-    if (!d_llr || !d_out || !d_cinit) return fail(OFDM_ERR_INVALID, "ofdm_descramble_llr_frames: null buffer");
-    GoldArgs a{};
-    a.in = d_llr;
-    a.out = d_out;
-    a.in_stride = seg_stride;
-    a.out_stride = out_stride;
-    a.n_seg = n_seg;
-    a.seg_bits = seg_bits;
-    a.cinit = d_cinit;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_gold_llr(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-int ofdm_crc_check_frames(ofdm_rx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_blocks, int32_t A, int32_t kind,
-                          uint32_t mask, const uint32_t* d_mask, const ofdm_crc_out* out, void* stream) {
-    const bool want_payload = out && out->payload;
-    const char* bad = crc_bad_args(kind, A, n_blocks, info_mode, want_payload ? out->payload_mode : info_mode, mask, d_mask);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: %s", bad);
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: null handle");
-    if (n_blocks == 0 || !out || (!out->ok && !out->syndrome && !out->payload)) return OFDM_OK;
-    if (!d_info) return fail(OFDM_ERR_INVALID, "ofdm_crc_check_frames: null d_info");
-    CrcArgs a{};
-    a.kind = kind;
-    a.A = A;
-    a.n_blocks = n_blocks;
-    a.mask = mask;
-    a.mask_dev = d_mask;
-    a.info_mode = info_mode;
-    a.payload_mode = want_payload ? out->payload_mode : info_mode;
-    a.info_in = d_info;
-    a.ok = out->ok;
-    a.syndrome = out->syndrome;
-    a.payload_out = out->payload;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_crc(a, pick_stream(h, stream)));
-    return OFDM_OK;
 }
 
 }  // extern "C"

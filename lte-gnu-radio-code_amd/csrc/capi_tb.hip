@@ -1,5 +1,5 @@
 // capi_tb.hip -- the transport-block layer of the LTE data channel on the frame-batched path (definition:
-// include/ofdm_mi355x.h): the segmentation and rate-matching arithmetic on the host, the long CRC on the host,
+// include/ofdm_mi355x.h): the segmentation and rate-matching arithmetic on the host
 // and the two calls that run a whole transport block -- segment, encode per group, concatenate on the transmitter handle;
 // de-match per group, decode per K, desegment on the receiver handle.  The encoder, the de-matcher and the decoder are reached
 // through their own public calls (capi_turbo.hip); everything those calls would refuse is refused here first, so that an
@@ -81,7 +81,7 @@ const char* tb_bad_call(int64_t n_tb, int32_t A, int32_t Z, int64_t G, int32_t q
     if (!turbo_qpp_valid(g->K_plus, f1p, f2p)) return "(f1_plus, f2_plus) is no permutation of 0 .. K_plus - 1";
     if (!d_rv && (rv < 0 || rv > 3)) return "rv must lie in 0 .. 3";
     const int64_t row = std::max(std::max(row_a, row_b), std::max<int64_t>(g->soft_floats, g->G));
-    if (n_tb > TBCC_MAX_BLOCKS / g->C || row > TB_MAX_ITEMS || (n_tb > 0 && row > TB_MAX_ITEMS / n_tb)) return "batch beyond the kernels' index range";
+    if (n_tb > MAX_BLOCKS / g->C || row > TB_MAX_ITEMS || (n_tb > 0 && row > TB_MAX_ITEMS / n_tb)) return "batch beyond the kernels' index range";
     return "";
 }
 
@@ -142,7 +142,7 @@ int rx_reserve_tb(ofdm_rx* h, int64_t n_tb, int32_t A, int32_t Z, bool es, const
     if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
     ofdm_tb_geom g;
     const char* bad = tb_plan(A, Z, 0, 0, 0, &g);
-    if (!*bad && (n_tb < 0 || n_tb > TBCC_MAX_BLOCKS / g.C || (n_tb > 0 && g.soft_floats > TB_MAX_ITEMS / n_tb)))
+    if (!*bad && (n_tb < 0 || n_tb > MAX_BLOCKS / g.C || (n_tb > 0 && g.soft_floats > TB_MAX_ITEMS / n_tb)))
         bad = "negative count or a batch beyond the kernels' index range";
     if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
     HIP_TRY(hipSetDevice(h->cfg.device));
@@ -176,7 +176,7 @@ int tb_decode(ofdm_rx* h, const float* d_llr, int64_t n_tb, int64_t llr_stride, 
         else if (llr_stride < G) bad = "llr_stride < G";
         else if (soft_stride < g.soft_floats) bad = "soft_stride < sum (3 K_r + 12)";
         else if (!out) bad = "null out";
-        else if (out->payload && !tbcc_bits_mode_ok(out->payload_mode)) bad = "payload_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else if (out->payload && !bits_mode_ok(out->payload_mode)) bad = "payload_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
     }
     if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", d.who, bad);
     if (n_tb == 0) return OFDM_OK;
@@ -250,19 +250,11 @@ int ofdm_tb_geometry(int32_t A, int32_t Z, int64_t G, int32_t q, int64_t N_IR, o
     return *bad ? fail(OFDM_ERR_INVALID, "ofdm_tb_geometry: %s", bad) : OFDM_OK;
 }
 
-int ofdm_crc_compute_long(int32_t kind, const uint8_t* host_bits_packed, int64_t n_bits, uint32_t* crc) {
-    if (kind < OFDM_CRC24A || kind > OFDM_CRC8) return fail(OFDM_ERR_INVALID, "ofdm_crc_compute_long: kind must be OFDM_CRC24A, OFDM_CRC24B, OFDM_CRC16 or OFDM_CRC8");
-    if (n_bits < 8 || n_bits > (int64_t(1) << 30) || n_bits % 8) return fail(OFDM_ERR_INVALID, "ofdm_crc_compute_long: n_bits must be a multiple of 8 with 8 <= n_bits <= 2^30");
-    if (!host_bits_packed || !crc) return fail(OFDM_ERR_INVALID, "ofdm_crc_compute_long: null argument");
-    *crc = crc_long_host(kind, host_bits_packed, n_bits >> 3);
-    return OFDM_OK;
-}
-
 int ofdm_tx_reserve_tb(ofdm_tx* h, int64_t n_tb, int32_t A, int32_t Z, int64_t G, int32_t q) {
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_tb: null handle");
     ofdm_tb_geom g;
     const char* bad = G == 0 ? "G must lie in 1 .. 2^31 - 1" : tb_plan(A, Z, G, q, 0, &g);
-    if (!*bad && (n_tb < 0 || n_tb > TBCC_MAX_BLOCKS / g.C || (n_tb > 0 && std::max<int64_t>(g.soft_floats, g.G) > TB_MAX_ITEMS / n_tb)))
+    if (!*bad && (n_tb < 0 || n_tb > MAX_BLOCKS / g.C || (n_tb > 0 && std::max<int64_t>(g.soft_floats, g.G) > TB_MAX_ITEMS / n_tb)))
         bad = "negative count or a batch beyond the kernels' index range";
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_tb: %s", bad);
     HIP_TRY(hipSetDevice(h->cfg.device));
@@ -282,7 +274,7 @@ int ofdm_tx_tb_encode_frames(ofdm_tx* h, const uint8_t* d_payload, int32_t paylo
     ofdm_tb_geom g;
     const char* bad = tb_bad_call(n_tb, A, Z, G, q, N_IR, f1_minus, f2_minus, f1_plus, f2_plus, rv, d_rv, cw_bits, 0, &g);
     if (!*bad) {
-        if (!tbcc_bits_mode_ok(payload_mode) || !tbcc_bits_mode_ok(cw_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        if (!bits_mode_ok(payload_mode) || !bits_mode_ok(cw_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
         else if (cw_bits < G) bad = "cw_bits < G";
         else if (cw_mode == OFDM_BITS_PACKED && (cw_bits & 7)) bad = "packed codewords need cw_bits % 8 == 0";
     }

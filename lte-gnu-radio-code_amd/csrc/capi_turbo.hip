@@ -10,7 +10,7 @@ constexpr const char* TURBO_BAD_K = "K must be a multiple of 8 with 40 <= K <= 6
 const char* turbo_bad_geometry(int64_t n_seg, int64_t blocks_per_seg, int64_t K, int64_t f1, int64_t f2) {
     if (!turbo_valid_k(K)) return TURBO_BAD_K;
     if (n_seg < 0 || blocks_per_seg < 0) return "negative count";
-    if (n_seg > TBCC_MAX_BLOCKS || blocks_per_seg > TBCC_MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS / blocks_per_seg))
+    if (n_seg > MAX_BLOCKS || blocks_per_seg > MAX_BLOCKS || (blocks_per_seg > 0 && n_seg > MAX_BLOCKS / blocks_per_seg))
         return "batch beyond the kernels' index range";
     if (f1 < 0 || f1 >= K || f2 < 0 || f2 >= K) return "f1 and f2 must lie in 0 .. K-1";
     if (!turbo_qpp_valid(K, f1, f2)) return "(f1 i + f2 i^2) mod K is not a permutation of 0 .. K-1";
@@ -26,11 +26,7 @@ const char* turbo_rm_bad_geometry(int32_t K, int64_t E, int64_t Ncb, int32_t rv,
     return "";
 }
 bool turbo_wanted(const ofdm_turbo_out* o) { return o && (o->bits || o->llr); }
-int turbo_ensure(ofdm_rx* h, int64_t n_blocks, int32_t K, hipStream_t s) {
-    if (turbo_ws_floats(n_blocks, K) <= h->cap_turbo) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo");
-    return rc != OFDM_OK ? rc : ofdm_rx_reserve_turbo(h, n_blocks, K);
-}
+constexpr const char* TURBO_SHORT_STRIDE = "seg_stride < blocks_per_seg * (3K + 12)";
 // both decoders share the handle's workspace: it holds `need` floats afterwards, and only grows
 int turbo_grow(ofdm_rx* h, int64_t need) {
     if (need <= h->cap_turbo) return OFDM_OK;
@@ -39,7 +35,7 @@ int turbo_grow(ofdm_rx* h, int64_t need) {
 const char* turbo_bad_reserve(int64_t n_blocks, int32_t K) {
     if (!turbo_valid_k(K)) return TURBO_BAD_K;
     if (n_blocks < 0) return "negative count";
-    if (n_blocks > TBCC_MAX_BLOCKS) return "batch beyond the kernel's index range";
+    if (n_blocks > MAX_BLOCKS) return "batch beyond the kernel's index range";
     return "";
 }
 bool turbo_es_wanted(const ofdm_turbo_es_out* o) { return o && (o->bits || o->llr || o->iters || o->crc_ok); }
@@ -62,23 +58,14 @@ int ofdm_tx_turbo_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_
                                 int32_t K, int32_t f1, int32_t f2, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: null handle");
     const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
-    if (!*bad) {
-        if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-        else if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_bits < blocks_per_seg * (3K + 12)";
-        else if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) bad = "packed coded bits need seg_bits % 8 == 0";
-        else if (!tbcc_items_ok(n_seg, seg_bits)) bad = "batch beyond the kernel's index range";
-    }
+    if (!*bad)
+        bad = enc_bad_args(info_mode, coded_mode, n_seg, seg_bits, int64_t(blocks_per_seg) * (3 * int64_t(K) + 12),
+                           "seg_bits < blocks_per_seg * (3K + 12)");
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: %s", bad);
     if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
     if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_frames: null buffer");
     TurboEncArgs a{};
-    a.info = d_info;
-    a.info_mode = info_mode;
-    a.n_seg = n_seg;
-    a.blocks_per_seg = blocks_per_seg;
-    a.coded = d_coded;
-    a.coded_mode = coded_mode;
-    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    enc_fill(a, d_info, info_mode, n_seg, blocks_per_seg, d_coded, coded_mode, seg_bits);
     a.q = turbo_qpp(K, f1, f2);
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(launch_turbo_encode(a, pick_stream(h, stream)));
@@ -102,9 +89,7 @@ int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int6
     const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
     if (!*bad) {
         if (n_iter < 1 || n_iter > TURBO_ITER_MAX) bad = "n_iter must lie in 1 .. 16";
-        else if (seg_stride < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_stride < blocks_per_seg * (3K + 12)";
-        else if (!tbcc_items_ok(n_seg, seg_stride)) bad = "batch beyond the kernel's index range";
-        else if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode)) bad = "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else bad = dec_bad_args(n_seg, seg_stride, int64_t(blocks_per_seg) * (3 * int64_t(K) + 12), TURBO_SHORT_STRIDE, out);
     }
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_frames: %s", bad);
     if (n_seg == 0 || blocks_per_seg == 0 || !turbo_wanted(out)) return OFDM_OK;
@@ -112,18 +97,14 @@ int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int6
     hipStream_t s = pick_stream(h, stream);
     const int64_t n_blocks = n_seg * blocks_per_seg;
     HIP_TRY(hipSetDevice(h->cfg.device));
-    const int rc = turbo_ensure(h, n_blocks, K, s);
+    const int rc = turbo_ensure(h, turbo_ws_floats(n_blocks, K), n_blocks, K, s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo",
+                                ofdm_rx_reserve_turbo);
     if (rc != OFDM_OK) return rc;
     TurboDecArgs a{};
-    a.llr = d_llr;
-    a.seg_stride = seg_stride;
-    a.n_blocks = n_blocks;
-    a.blocks_per_seg = blocks_per_seg;
+    dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, out);
     a.n_iter = n_iter;
     a.ext = h->t_ws;
     a.ckpt = h->t_ws + n_blocks * K;
-    a.bits = out->bits;
-    a.bits_mode = out->bits_mode;
     a.llr_out = out->llr;
     a.q = turbo_qpp(K, f1, f2);
     HIP_TRY(launch_turbo_decode(a, s));
@@ -148,11 +129,9 @@ int ofdm_turbo_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, i
     if (!*bad) {
         if (crc_kind < OFDM_CRC24A || crc_kind > OFDM_CRC8) bad = "crc_kind must be OFDM_CRC24A, OFDM_CRC24B, OFDM_CRC16 or OFDM_CRC8";
         else if (min_iter < 1 || max_iter > TURBO_ITER_MAX || min_iter > max_iter) bad = "1 <= min_iter <= max_iter <= 16 does not hold";
-        else if (seg_stride < int64_t(blocks_per_seg) * (3 * int64_t(K) + 12)) bad = "seg_stride < blocks_per_seg * (3K + 12)";
-        else if (!tbcc_items_ok(n_seg, seg_stride)) bad = "batch beyond the kernel's index range";
-        else if (out && out->bits && !tbcc_bits_mode_ok(out->bits_mode)) bad = "bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        else if (*(bad = dec_bad_args(n_seg, seg_stride, int64_t(blocks_per_seg) * (3 * int64_t(K) + 12), TURBO_SHORT_STRIDE, out))) {}
         else if (out && out->stat_stride != 0 && out->stat_stride < blocks_per_seg) bad = "stat_stride must be 0 or >= blocks_per_seg";
-        else if (out && !tbcc_items_ok(n_seg, out->stat_stride)) bad = "batch beyond the kernel's index range";
+        else if (out && !batch_items_ok(n_seg, out->stat_stride)) bad = "batch beyond the kernel's index range";
     }
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_decode_es_frames: %s", bad);
     if (n_seg == 0 || blocks_per_seg == 0 || !turbo_es_wanted(out)) return OFDM_OK;
@@ -160,24 +139,17 @@ int ofdm_turbo_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, i
     hipStream_t s = pick_stream(h, stream);
     const int64_t n_blocks = n_seg * blocks_per_seg;
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (turbo_es_ws_floats(n_blocks, K) > h->cap_turbo) {
-        int rc = refuse_growth_in_capture(s, "ofdm_turbo_decode_es_frames", "ofdm_rx_reserve_turbo_es");
-        if (rc == OFDM_OK) rc = ofdm_rx_reserve_turbo_es(h, n_blocks, K);
-        if (rc != OFDM_OK) return rc;
-    }
+    const int rc = turbo_ensure(h, turbo_es_ws_floats(n_blocks, K), n_blocks, K, s, "ofdm_turbo_decode_es_frames",
+                                "ofdm_rx_reserve_turbo_es", ofdm_rx_reserve_turbo_es);
+    if (rc != OFDM_OK) return rc;
     TurboDecEsArgs a{};
-    a.llr = d_llr;
-    a.seg_stride = seg_stride;
-    a.n_blocks = n_blocks;
-    a.blocks_per_seg = blocks_per_seg;
+    dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, out);
     a.min_iter = min_iter;
     a.max_iter = max_iter;
     a.crc_kind = crc_kind;
     a.ext = h->t_ws;
     a.post = a.ext + n_blocks * K;
     a.ckpt = a.post + n_blocks * K;
-    a.bits = out->bits;
-    a.bits_mode = out->bits_mode;
     a.llr_out = out->llr;
     a.iters = out->iters;
     a.crc_ok = out->crc_ok;
@@ -205,19 +177,8 @@ int ofdm_turbo_rm_info(int32_t K, int32_t Ncb, int32_t rv, int32_t* k0, int32_t*
     return OFDM_OK;
 }
 
-int ofdm_tx_reserve_turbo_rm(ofdm_tx* h) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_turbo_rm: null handle");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(turbo_rm_prepare());
-    return OFDM_OK;
-}
-
-int ofdm_rx_reserve_turbo_rm(ofdm_rx* h) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_turbo_rm: null handle");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(turbo_rm_prepare());
-    return OFDM_OK;
-}
+int ofdm_tx_reserve_turbo_rm(ofdm_tx* h) { return prepare_only(h, "ofdm_tx_reserve_turbo_rm", turbo_rm_prepare); }
+int ofdm_rx_reserve_turbo_rm(ofdm_rx* h) { return prepare_only(h, "ofdm_rx_reserve_turbo_rm", turbo_rm_prepare); }
 
 int ofdm_tx_turbo_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
                                    int32_t K, int32_t f1, int32_t f2, int32_t E, int32_t Ncb, int32_t rv, const int32_t* d_rv,
@@ -225,23 +186,12 @@ int ofdm_tx_turbo_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t in
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: null handle");
     const char* bad = turbo_bad_geometry(n_seg, blocks_per_seg, K, f1, f2);
     if (!*bad) bad = turbo_rm_bad_geometry(K, E, Ncb, rv, d_rv);
-    if (!*bad) {
-        if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode)) bad = "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-        else if (seg_bits < 0 || seg_bits < int64_t(blocks_per_seg) * E) bad = "seg_bits < blocks_per_seg * E";
-        else if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) bad = "packed coded bits need seg_bits % 8 == 0";
-        else if (!tbcc_items_ok(n_seg, seg_bits)) bad = "batch beyond the kernel's index range";
-    }
+    if (!*bad) bad = enc_bad_args(info_mode, coded_mode, n_seg, seg_bits, int64_t(blocks_per_seg) * E, "seg_bits < blocks_per_seg * E");
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: %s", bad);
     if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
     if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_turbo_encode_rm_frames: null buffer");
     TurboEncRmArgs a{};
-    a.info = d_info;
-    a.info_mode = info_mode;
-    a.n_seg = n_seg;
-    a.blocks_per_seg = blocks_per_seg;
-    a.coded = d_coded;
-    a.coded_mode = coded_mode;
-    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
+    enc_fill(a, d_info, info_mode, n_seg, blocks_per_seg, d_coded, coded_mode, seg_bits);
     a.q = turbo_qpp(K, f1, f2);
     a.g = turbo_rm_geom(K, E, Ncb);
     a.rv = rv;
@@ -263,8 +213,8 @@ int ofdm_turbo_rate_dematch_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg
     else if (seg_stride < int64_t(blocks_per_seg) * E) bad = "seg_stride < blocks_per_seg * E";
     else if (out_stride < int64_t(blocks_per_seg) * per) bad = "out_stride < blocks_per_seg * (3K + 12)";
     // one thread per output LLR in workgroups of 256: the grid's x range bounds n_seg * blocks_per_seg * (3K + 12)
-    else if (!tbcc_items_ok(n_seg, seg_stride) || !tbcc_items_ok(n_seg, out_stride) || n_seg > TBCC_MAX_BLOCKS ||
-             (blocks_per_seg > 0 && n_seg > TBCC_MAX_BLOCKS * int64_t(256) / per / blocks_per_seg))
+    else if (!batch_items_ok(n_seg, seg_stride) || !batch_items_ok(n_seg, out_stride) || n_seg > MAX_BLOCKS ||
+             (blocks_per_seg > 0 && n_seg > MAX_BLOCKS * int64_t(256) / per / blocks_per_seg))
         bad = "batch beyond the kernel's index range";
     if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_turbo_rate_dematch_frames: %s", bad);
     if (n_seg == 0 || blocks_per_seg == 0) return OFDM_OK;

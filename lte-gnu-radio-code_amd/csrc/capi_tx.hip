@@ -1,32 +1,6 @@
-// capi_tx.hip -- the transmitter handle: create / destroy, TBCC encode (plain and rate-matched), CRC attach and scrambling, the
-// decomposed stages, ofdm_tx_modulate_frames and ofdm_channel_apply.
+// capi_tx.hip -- the transmitter handle: create / destroy, the decomposed stages, ofdm_tx_modulate_frames and
+// ofdm_channel_apply.  Its codec calls live with their codecs (capi_tbcc.hip, capi_bitproc.hip, capi_turbo.hip, capi_tb.hip).
 #include "capi_internal.hpp"
-
-// ---- LTE tail-biting convolutional code on the frame-batched path (definition: include/ofdm_mi355x.h, DESIGN.md 9.2.3, and
-// its rate matching, TS 36.212 5.1.4.2): encode
-namespace {
-// what the two encodes check after their geometry: `need` coded bits per segment (blocks_per_seg * 3K, or * E rate-matched),
-// `short_text` the text for a shorter segment; "" = fine
-const char* tbcc_enc_bad_args(int32_t info_mode, int32_t coded_mode, int64_t n_seg, int64_t seg_bits, int64_t need, const char* short_text) {
-    if (!tbcc_bits_mode_ok(info_mode) || !tbcc_bits_mode_ok(coded_mode)) return "bit modes must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-    if (seg_bits < 0 || seg_bits < need) return short_text;
-    if (coded_mode == OFDM_BITS_PACKED && (seg_bits & 7)) return "packed coded bits need seg_bits % 8 == 0";
-    if (!tbcc_items_ok(n_seg, seg_bits)) return "batch beyond the kernel's index range";
-    return "";
-}
-template <class Args>
-void tbcc_enc_fill(Args& a, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg, int32_t K, uint8_t* d_coded,
-                   int32_t coded_mode, int64_t seg_bits) {
-    a.info = d_info;
-    a.info_mode = info_mode;
-    a.n_seg = n_seg;
-    a.blocks_per_seg = blocks_per_seg;
-    a.K = K;
-    a.coded = d_coded;
-    a.coded_mode = coded_mode;
-    a.seg_bytes = coded_mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
-}
-}  // namespace
 
 extern "C" {
 
@@ -92,89 +66,6 @@ int ofdm_tx_create(const ofdm_tx_cfg* c, ofdm_tx** out) {
         if (rc != OFDM_OK) return create_failed(h, rc, ofdm_tx_destroy);
     }
     *out = h;
-    return OFDM_OK;
-}
-
-int ofdm_tx_tbcc_encode_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
-                               int32_t K, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: null handle");
-    const char* bad = tbcc_bad_geometry(n_seg, blocks_per_seg, K);
-    if (!*bad)
-        bad = tbcc_enc_bad_args(info_mode, coded_mode, n_seg, seg_bits, int64_t(blocks_per_seg) * 3 * K, "seg_bits < blocks_per_seg * 3K");
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: %s", bad);
-    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
-    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_frames: null buffer");
-    TbccEncArgs a{};
-    tbcc_enc_fill(a, d_info, info_mode, n_seg, blocks_per_seg, K, d_coded, coded_mode, seg_bits);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_tbcc_encode(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-int ofdm_tx_tbcc_encode_rm_frames(ofdm_tx* h, const uint8_t* d_info, int32_t info_mode, int64_t n_seg, int32_t blocks_per_seg,
-                                  int32_t K, int32_t E, uint8_t* d_coded, int32_t coded_mode, int64_t seg_bits, void* stream) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: null handle");
-    const char* bad = tbcc_rm_bad_geometry(n_seg, blocks_per_seg, K, E);
-    if (!*bad) bad = tbcc_enc_bad_args(info_mode, coded_mode, n_seg, seg_bits, int64_t(blocks_per_seg) * E, "seg_bits < blocks_per_seg * E");
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: %s", bad);
-    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
-    if (!d_coded || (blocks_per_seg > 0 && !d_info)) return fail(OFDM_ERR_INVALID, "ofdm_tx_tbcc_encode_rm_frames: null buffer");
-    TbccEncRmArgs a{};
-    tbcc_enc_fill(a, d_info, info_mode, n_seg, blocks_per_seg, K, d_coded, coded_mode, seg_bits);
-    a.g = tbcc_rm_geom(K, E);
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_tbcc_encode_rm(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-// ---- CRC attach and Gold-sequence scrambling (definition: include/ofdm_mi355x.h)
-int ofdm_tx_reserve_bitproc(ofdm_tx* h) {
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_bitproc: null handle");
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(bitproc_prepare());
-    return OFDM_OK;
-}
-
-int ofdm_tx_crc_attach_frames(ofdm_tx* h, const uint8_t* d_payload, int32_t payload_mode, int64_t n_blocks, int32_t A, int32_t kind,
-                              uint32_t mask, const uint32_t* d_mask, uint8_t* d_info, int32_t info_mode, void* stream) {
-    const char* bad = crc_bad_args(kind, A, n_blocks, payload_mode, info_mode, mask, d_mask);
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_crc_attach_frames: %s", bad);
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_crc_attach_frames: null handle");
-    if (n_blocks == 0) return OFDM_OK;
-    if (!d_payload || !d_info) return fail(OFDM_ERR_INVALID, "ofdm_tx_crc_attach_frames: null buffer");
-    CrcArgs a{};
-    a.kind = kind;
-    a.A = A;
-    a.n_blocks = n_blocks;
-    a.mask = mask;
-    a.mask_dev = d_mask;
-    a.info_mode = info_mode;
-    a.payload_mode = payload_mode;
-    a.payload_in = d_payload;
-    a.info_out = d_info;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_crc(a, pick_stream(h, stream)));
-    return OFDM_OK;
-}
-
-int ofdm_tx_scramble_frames(ofdm_tx* h, const uint8_t* d_in, int32_t mode, int64_t n_seg, int64_t seg_bits, const uint32_t* d_cinit,
-                            uint8_t* d_out, void* stream) {
-    const char* bad = gold_bad_args(n_seg, seg_bits, seg_bits, seg_bits);
-    if (!*bad && !tbcc_bits_mode_ok(mode)) bad = "mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
-    if (!*bad && mode == OFDM_BITS_PACKED && (seg_bits & 7)) bad = "packed bits need seg_bits % 8 == 0";
-    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_tx_scramble_frames: %s", bad);
-    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_scramble_frames: null handle");
-    if (n_seg == 0 || seg_bits == 0) return OFDM_OK;
-    if (!d_in || !d_out || !d_cinit) return fail(OFDM_ERR_INVALID, "ofdm_tx_scramble_frames: null buffer");
-    GoldArgs a{};
-    a.in = d_in;
-    a.out = d_out;
-    a.in_stride = a.out_stride = mode == OFDM_BITS_PACKED ? seg_bits >> 3 : seg_bits;
-    a.n_seg = n_seg;
-    a.seg_bits = seg_bits;
-    a.cinit = d_cinit;
-    HIP_TRY(hipSetDevice(h->cfg.device));
-    HIP_TRY(launch_gold_bits(a, mode == OFDM_BITS_PACKED, pick_stream(h, stream)));
     return OFDM_OK;
 }
 

@@ -8,6 +8,16 @@
 
 namespace ofdm {
 
+// Loads the code objects of the given kernels, so that a first launch inside a stream capture has nothing left to set up (the
+// *_prepare() calls below); the first error, or hipSuccess.
+template <class... Kernel>
+inline hipError_t load_kernels(Kernel*... kernels) {
+    hipFuncAttributes fa;
+    hipError_t e = hipSuccess;
+    ((e = e == hipSuccess ? hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kernels)) : e), ...);
+    return e;
+}
+
 // ---- RX data demod (reference: SynchAndChanEst.py:221-248, "Loop B") --------------------------
 struct DemodArgs {
     const cf* iq;            // frames, frame f at iq + f*frame_stride

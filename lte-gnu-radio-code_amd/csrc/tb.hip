@@ -218,15 +218,6 @@ hipError_t launch_tb_concat(const TbConcatArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t tb_prepare() {
-    hipFuncAttributes fa;
-    const void* fns[] = {reinterpret_cast<const void*>(tb_segment_kernel), reinterpret_cast<const void*>(tb_desegment_kernel),
-                         reinterpret_cast<const void*>(tb_concat_kernel)};
-    for (const void* f : fns) {
-        const hipError_t e = hipFuncGetAttributes(&fa, f);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+hipError_t tb_prepare() { return load_kernels(tb_segment_kernel, tb_desegment_kernel, tb_concat_kernel); }
 
 }  // namespace ofdm

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include <type_traits>
+#include "codec_device.hpp"
 #include "ofdm_launch.hpp"
 
 namespace ofdm {
@@ -16,10 +17,6 @@ namespace {
 constexpr unsigned TBCC_G0 = 0133, TBCC_G1 = 0171, TBCC_G2 = 0165;   // bit 6 = current input, bit 6-i = delay i
 
 // ------------------------------------------------------------------------------------------ encoder
-__device__ __forceinline__ unsigned tbcc_info_bit(const uint8_t* blk, int packed, int i) {
-    return packed ? (unsigned(blk[i >> 3]) >> (7 - (i & 7))) & 1u : unsigned(blk[i]) & 1u;
-}
-
 // dj[k] of the block at blk: the parity of generator j over the 7-bit window that ends at k
 __device__ __forceinline__ unsigned tbcc_stream_bit(const uint8_t* blk, int info_packed, int K, int k, int j) {
     unsigned reg = 0u;                                   // bit 6-i = c[(k - i) mod K]
@@ -27,7 +24,7 @@ __device__ __forceinline__ unsigned tbcc_stream_bit(const uint8_t* blk, int info
     for (int i = 0; i < 7; ++i) {
         int idx = k - i;
         if (idx < 0) idx += K;
-        reg |= tbcc_info_bit(blk, info_packed, idx) << (6 - i);
+        reg |= info_bit(blk, info_packed, idx) << (6 - i);
     }
     const unsigned g = j == 0 ? TBCC_G0 : j == 1 ? TBCC_G1 : TBCC_G2;
     return unsigned(__popc(reg & g)) & 1u;
@@ -138,17 +135,13 @@ __global__ void __launch_bounds__(256) tbcc_encode_rm_kernel(TbccEncRmArgs a) {
     }
 }
 
-__device__ __forceinline__ float tbcc_finite_or_zero(float v) {
-    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
-}
-
 // De-matching of one coded bit: l = the block's E LLRs, q = the bit's rank, n3 = 3K.  The copies are added in increasing index,
 // one float32 addition each; a punctured bit is +0.  No product: nothing here for the compiler to contract.
 __device__ __forceinline__ float tbcc_rm_combine(const float* l, int E, int n3, int q) {
     float L = 0.f;
     if (q < E) {
-        L = tbcc_finite_or_zero(l[q]);
-        for (int idx = q + n3; idx < E; idx += n3) L = L + tbcc_finite_or_zero(l[idx]);
+        L = finite_or_zero(l[q]);
+        for (int idx = q + n3; idx < E; idx += n3) L = L + finite_or_zero(l[idx]);
     }
     return L;
 }
@@ -180,13 +173,6 @@ __global__ void __launch_bounds__(256) tbcc_dematch_kernel(TbccDematchArgs a) {
 // Arithmetic (the contract fixes fp32 and the order): sigma_j is +-1, so sigma_j * l_j is exact and
 // fma(sigma_1, l_1, sigma_0 * l_0) rounds once, exactly like (sigma_0 l_0 + sigma_1 l_1); the same holds for the third term.
 // The fma calls below are therefore the written order, and there is no other product in the metric path to contract.
-__device__ __forceinline__ float tbcc_readlane(float v, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ __forceinline__ float tbcc_bperm(int byte_addr, float v) {
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
-}
-
 // RM = false is the plain decoder.  RM = true de-matches in the tile load: the lane that owns step t takes its three LLRs
 // straight from the block's E rate-matched floats (tbcc_rm_combine, and a sum that is not finite counts as 0 like any other
 // input), so a rate-matched block is decoded in one launch with no 3K-float intermediate.  Everything behind the tile load is
@@ -220,13 +206,13 @@ __global__ void __launch_bounds__(64) tbcc_viterbi_kernel(std::conditional_t<RM,
             const int i = (base + lane + 4 * K - W) % K;     // (t - W) mod K; 4K >= W for every K >= 24
             if constexpr (RM) {
                 const int q = tbcc_rm_rank0(a.g, i);
-                l0 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q));
-                l1 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + K));
-                l2 = tbcc_finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + 2 * K));
+                l0 = finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q));
+                l1 = finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + K));
+                l2 = finite_or_zero(tbcc_rm_combine(llr, a.g.E, 3 * K, q + 2 * K));
             } else {
-                l0 = tbcc_finite_or_zero(llr[3 * i]);
-                l1 = tbcc_finite_or_zero(llr[3 * i + 1]);
-                l2 = tbcc_finite_or_zero(llr[3 * i + 2]);
+                l0 = finite_or_zero(llr[3 * i]);
+                l1 = finite_or_zero(llr[3 * i + 1]);
+                l2 = finite_or_zero(llr[3 * i + 2]);
             }
         }
         for (int h = 0; h < 2; ++h) {
@@ -237,10 +223,10 @@ __global__ void __launch_bounds__(64) tbcc_viterbi_kernel(std::conditional_t<RM,
 #pragma unroll
                 for (int v = 0; v < 8; ++v) {
                     const int src = 32 * h + u + v;
-                    const float bm = __builtin_fmaf(sg2, tbcc_readlane(l2, src),
-                                                    __builtin_fmaf(sg1, tbcc_readlane(l1, src), sg0 * tbcc_readlane(l0, src)));
-                    const float c0 = tbcc_bperm(addr0, pm) + bm;
-                    const float c1 = tbcc_bperm(addr1, pm) - bm;
+                    const float bm = __builtin_fmaf(sg2, readlane(l2, src),
+                                                    __builtin_fmaf(sg1, readlane(l1, src), sg0 * readlane(l0, src)));
+                    const float c0 = bperm(addr0, pm) + bm;
+                    const float c1 = bperm(addr1, pm) - bm;
                     const bool d = c1 > c0;
                     pm = d ? c1 : c0;
                     dec |= (d ? 1u : 0u) << (u + v);
@@ -360,10 +346,6 @@ hipError_t launch_tbcc_decode_rm(const TbccDecRmArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t tbcc_decode_prepare() {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(tbcc_viterbi_kernel<false>));
-    return e != hipSuccess ? e : hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(tbcc_viterbi_kernel<true>));
-}
+hipError_t tbcc_decode_prepare() { return load_kernels(tbcc_viterbi_kernel<false>, tbcc_viterbi_kernel<true>); }
 
 }  // namespace ofdm

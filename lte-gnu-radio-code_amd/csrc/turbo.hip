@@ -59,8 +59,8 @@ __global__ void __launch_bounds__(64) turbo_encode_kernel(TurboEncArgs a) {
     if (has) {
         unsigned p = p_begin, g = g_begin;
         for (int k = k_begin; k < k_end; ++k) {
-            s1 = turbo_rsc_step(s1, turbo_info_bit(info, info_packed, unsigned(k)), z);
-            s2 = turbo_rsc_step(s2, turbo_info_bit(info, info_packed, p), z);
+            s1 = turbo_rsc_step(s1, info_bit(info, info_packed, unsigned(k)), z);
+            s2 = turbo_rsc_step(s2, info_bit(info, info_packed, p), z);
             p = turbo_mod_add(p, g, uK);
             g = turbo_mod_add(g, unsigned(a.q.g2), uK);
         }
@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(64) turbo_encode_kernel(TurboEncArgs a) {
         s1 = in1;
         s2 = in2;
         for (int k = k_begin; k < k_end; ++k) {
-            s1 = turbo_rsc_step(s1, turbo_info_bit(info, info_packed, unsigned(k)), z1);
-            s2 = turbo_rsc_step(s2, turbo_info_bit(info, info_packed, p), z2);
+            s1 = turbo_rsc_step(s1, info_bit(info, info_packed, unsigned(k)), z1);
+            s2 = turbo_rsc_step(s2, info_bit(info, info_packed, p), z2);
             sm_z[half * K + k] = uint8_t(z1 | (z2 << 1));
             p = turbo_mod_add(p, g, uK);
             g = turbo_mod_add(g, unsigned(a.q.g2), uK);
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(64) turbo_encode_kernel(TurboEncArgs a) {
         r -= lb * blk_bits;
         if (r >= 3 * K) return (sm_tail[lb] >> (11 - int(r - 3 * K))) & 1u;
         const int k = int(r) / 3, j = int(r) - 3 * k;
-        if (j == 0) return turbo_info_bit(pair_info + int64_t(lb) * blk_bytes, info_packed, unsigned(k));
+        if (j == 0) return info_bit(pair_info + int64_t(lb) * blk_bytes, info_packed, unsigned(k));
         return (unsigned(sm_z[lb * K + k]) >> (j - 1)) & 1u;
     };
     uint8_t* seg_out = a.coded + seg * a.seg_bytes;
@@ -246,9 +246,6 @@ hipError_t launch_turbo_decode(const TurboDecArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t turbo_decode_prepare() {
-    hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(turbo_decode_kernel));
-}
+hipError_t turbo_decode_prepare() { return load_kernels(turbo_decode_kernel); }
 
 }  // namespace ofdm

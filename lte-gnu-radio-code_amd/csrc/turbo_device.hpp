@@ -1,8 +1,9 @@
 // turbo_device.hpp -- the device routines the turbo encoders share (turbo.hip, turbo_rm.hip): the QPP interleaver in 32-bit
-// arithmetic, the information-bit fetch and the constituent encoder's step, free response and termination.
+// arithmetic and the constituent encoder's step, free response and termination (the information-bit fetch: codec_device.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "codec_device.hpp"
 #include "ofdm_launch.hpp"
 
 namespace ofdm {
@@ -19,9 +20,6 @@ __device__ __forceinline__ unsigned turbo_mod_add(unsigned a, unsigned b, unsign
     return s >= K ? s - K : s;
 }
 
-__device__ __forceinline__ unsigned turbo_info_bit(const uint8_t* blk, int packed, unsigned i) {
-    return packed ? (unsigned(blk[i >> 3]) >> (7 - (i & 7))) & 1u : unsigned(blk[i]) & 1u;
-}
 // one step of a constituent encoder: state s = 4 r1 + 2 r2 + r3, input u -> parity z, next state
 __device__ __forceinline__ unsigned turbo_rsc_step(unsigned s, unsigned u, unsigned& z) {
     const unsigned r1 = s >> 2, r2 = (s >> 1) & 1u, r3 = s & 1u;

@@ -132,9 +132,6 @@ hipError_t launch_turbo_decode_es(const TurboDecEsArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t turbo_decode_es_prepare() {
-    hipFuncAttributes fa;
-    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(turbo_decode_es_kernel));
-}
+hipError_t turbo_decode_es_prepare() { return load_kernels(turbo_decode_es_kernel); }
 
 }  // namespace ofdm

@@ -83,8 +83,8 @@ __global__ void __launch_bounds__(64) turbo_encode_rm_kernel(TurboEncRmArgs a, i
         {
             unsigned p = p_begin, g = g_begin;
             for (int k = k_begin; k < k_end; ++k) {
-                s1 = turbo_rsc_step(s1, turbo_info_bit(info, info_packed, unsigned(k)), z);
-                s2 = turbo_rsc_step(s2, turbo_info_bit(info, info_packed, p), z);
+                s1 = turbo_rsc_step(s1, info_bit(info, info_packed, unsigned(k)), z);
+                s2 = turbo_rsc_step(s2, info_bit(info, info_packed, p), z);
                 p = turbo_mod_add(p, g, uK);
                 g = turbo_mod_add(g, unsigned(a.q.g2), uK);
             }
@@ -104,9 +104,9 @@ __global__ void __launch_bounds__(64) turbo_encode_rm_kernel(TurboEncRmArgs a, i
             s1 = in1;
             s2 = in2;
             for (int k = k_begin; k < k_end; ++k) {
-                const unsigned c = turbo_info_bit(info, info_packed, unsigned(k));
+                const unsigned c = info_bit(info, info_packed, unsigned(k));
                 s1 = turbo_rsc_step(s1, c, z1);
-                s2 = turbo_rsc_step(s2, turbo_info_bit(info, info_packed, p), z2);
+                s2 = turbo_rsc_step(s2, info_bit(info, info_packed, p), z2);
                 const int n0 = turbo_rm_first(a.g, 0, k, 0), n1 = turbo_rm_first(a.g, 0, k, 1), n2 = turbo_rm_first(a.g, 0, k, 2);
                 if (n0 >= 0) sm_w[n0] = uint8_t(c);
                 if (n1 >= 0) sm_w[n1] = uint8_t(z1);
@@ -181,10 +181,6 @@ __global__ void __launch_bounds__(64) turbo_encode_rm_kernel(TurboEncRmArgs a, i
 }
 
 // ------------------------------------------------------------------------------------------ de-matching
-__device__ __forceinline__ float turbo_rm_finite_or_zero(float v) {
-    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
-}
-
 // tbcc_dematch_kernel's shape: one thread per output LLR (segment, block, 3i + j), the grid is exactly the work.  The stores are
 // coalesced; the <= 16 reads per thread are scattered over the block's own E floats.  The copies are added in increasing index,
 // one float32 addition each, a bit that is never sent is +0; with accumulate the float already there is added last.  No
@@ -202,8 +198,8 @@ __global__ void __launch_bounds__(256) turbo_dematch_kernel(TurboDematchArgs a) 
     const int n0 = turbo_rm_first(a.g, turbo_rm_rank0(a.g, turbo_rm_rv(a.rv, a.rv_dev, seg)), i, j);
     float L = 0.f;
     if (n0 >= 0 && n0 < a.g.E) {
-        L = turbo_rm_finite_or_zero(l[n0]);
-        for (int idx = n0 + a.g.navail; idx < a.g.E; idx += a.g.navail) L = L + turbo_rm_finite_or_zero(l[idx]);
+        L = finite_or_zero(l[n0]);
+        for (int idx = n0 + a.g.navail; idx < a.g.E; idx += a.g.navail) L = L + finite_or_zero(l[idx]);
     }
     float* out = a.out + seg * a.out_stride + int64_t(b) * per + x;
     *out = a.accumulate ? *out + L : L;
@@ -252,10 +248,6 @@ hipError_t launch_turbo_dematch(const TurboDematchArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t turbo_rm_prepare() {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(turbo_encode_rm_kernel));
-    return e != hipSuccess ? e : hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(turbo_dematch_kernel));
-}
+hipError_t turbo_rm_prepare() { return load_kernels(turbo_encode_rm_kernel, turbo_dematch_kernel); }
 
 }  // namespace ofdm

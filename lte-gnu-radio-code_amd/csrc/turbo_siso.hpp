@@ -18,12 +18,6 @@ namespace ofdm {
 
 namespace {
 
-__device__ __forceinline__ float turbo_finite_or_zero(float v) {
-    return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u ? 0.f : v;
-}
-__device__ __forceinline__ float turbo_bperm(int byte_addr, float v) {
-    return __int_as_float(__builtin_amdgcn_ds_bpermute(byte_addr, __float_as_int(v)));
-}
 __device__ __forceinline__ float turbo_group_max(float v) {
     v = fmaxf(v, __shfl_xor(v, 1, 64));
     v = fmaxf(v, __shfl_xor(v, 2, 64));
@@ -85,8 +79,8 @@ __device__ __forceinline__ void turbo_half_iteration(const TurboQpp& q, const fl
             const unsigned idx = half ? p : i;
             if (active) {
                 const float la = first ? 0.f : ext[idx];
-                x = turbo_finite_or_zero(llr[3 * idx]) + la;
-                lp = turbo_finite_or_zero(llr[3 * i + 1 + half]);
+                x = finite_or_zero(llr[3 * idx]) + la;
+                lp = finite_or_zero(llr[3 * i + 1 + half]);
             }
             my_x[j] = make_float2(x, lp);
             my_i[j] = int(idx);
@@ -103,10 +97,10 @@ __device__ __forceinline__ void turbo_half_iteration(const TurboQpp& q, const fl
                 const float2 xl = my_x[j8 + v];
                 if (keep) sm_a[((j8 + v) << 6) + lane] = A;
                 const float gm = __builtin_fmaf(c.f_sz, xl.y, c.f_su * xl.x);
-                const float c0 = turbo_bperm(c.addr_p0, A) + gm;
-                const float c1 = turbo_bperm(c.addr_p1, A) - gm;
+                const float c0 = bperm(c.addr_p0, A) + gm;
+                const float c1 = bperm(c.addr_p1, A) - gm;
                 A = fmaxf(c0, c1);
-                if (v == 7) A = A - turbo_bperm(c.addr_s0, A);
+                if (v == 7) A = A - bperm(c.addr_s0, A);
             }
         }
         return A;
@@ -124,12 +118,12 @@ __device__ __forceinline__ void turbo_half_iteration(const TurboQpp& q, const fl
     {
         float t[6];
 #pragma unroll
-        for (int j = 0; j < 6; ++j) t[j] = active ? turbo_finite_or_zero(llr[3 * K + 6 * half + j]) : 0.f;
+        for (int j = 0; j < 6; ++j) t[j] = active ? finite_or_zero(llr[3 * K + 6 * half + j]) : 0.f;
         const float g0 = __builtin_fmaf(c.t_s1, t[1], c.t_s0 * t[0]);
         const float g1 = __builtin_fmaf(c.t_s3, t[3], c.t_s2 * t[2]);
         const float g2 = __builtin_fmaf(c.t_s4, t[5], c.t_s4 * t[4]);
         const float bs = (g0 + g1) + g2;
-        B = bs - turbo_bperm(c.addr_s0, bs);
+        B = bs - bperm(c.addr_s0, bs);
     }
 
     for (int t = n_tiles - 1; t >= 0; --t) {
@@ -143,7 +137,7 @@ __device__ __forceinline__ void turbo_half_iteration(const TurboQpp& q, const fl
                 const float2 xl = my_x[j8 + v];
                 const float Ak = sm_a[((j8 + v) << 6) + lane];
                 const float gm = __builtin_fmaf(c.b_sz, xl.y, xl.x);                 // gamma of input 0; input 1 has -gamma
-                const float b0 = turbo_bperm(c.addr_n0, B), b1 = turbo_bperm(c.addr_n1, B);
+                const float b0 = bperm(c.addr_n0, B), b1 = bperm(c.addr_n1, B);
                 const float m0 = turbo_group_max((Ak + gm) + b0);
                 const float m1 = turbo_group_max((Ak - gm) + b1);
                 const float post = 0.5f * (m0 - m1);
@@ -157,7 +151,7 @@ __device__ __forceinline__ void turbo_half_iteration(const TurboQpp& q, const fl
                     }
                 }
                 float nb = fmaxf(gm + b0, b1 - gm);
-                if (v == 0) nb = nb - turbo_bperm(c.addr_s0, nb);
+                if (v == 0) nb = nb - bperm(c.addr_s0, nb);
                 B = nb;
             }
             if (store) {
