@@ -370,6 +370,54 @@ int64_t ofdm_rx_demod_frames_mrc(ofdm_rx* h, const float* d_iq, int32_t n_branch
                                  int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
                                  const double* h_noise_var, const ofdm_mrc_out* out, double* d_sigma2_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ delay-window channel-estimate denoising
+ * An extension the reference does not have.  The batch receiver's channel estimate is the least-squares (LS) estimate of ONE
+ * Zadoff-Chu preamble symbol: as noisy as one received symbol.  A channel is shorter than the cyclic prefix, so nearly all of that
+ * noise lies at delays where the channel has no energy: the stage transforms the estimate to the delay domain, keeps a window of
+ * taps around tap 0 and transforms back (DFT-based denoising).  This text is the definition; tests/chanwin_ref.py restates it in
+ * fp64 NumPy.  The library computes in float32 with an FFT whose operation order is its own: it agrees with the definition to
+ * max|a - b| / max|b| < 1e-5 per output row (the bar of every FFT-based output of this library), not bit for bit.
+ *
+ * Per row (frame) with a sync (tsr[3] == 1), N = nfft, window (pre, post) with pre >= 0, post >= 1 and pre + post <= N:
+ *  1. h = ifft_N(H_ls).  H_ls is the frame's est_chan_freq_P row: zero outside the sync bins, with the lag de-rotation already
+ *     applied, so the energy sits around tap 0.
+ *  2. Keep h[n] for n in [0, post) and [N - pre, N); set the other M = N - pre - post taps to zero.
+ *  3. tail = (N / M) * sum over the discarded n of |h[n]|^2: float32, the order of the sum fixed by N alone, so the same bits alone,
+ *     in any batch and on every call.  M == 0 gives tail = +0.
+ *  4. H' = fft_N(the windowed h) on the sync bins binsP(num_synch_bins), +0 on every other bin.  (num_synch_bins == nfft lists
+ *     bin N/2 twice; est_chan_freq_P holds one value there and so does H'.)
+ *  5. gain[j], j over binsP(num_data_bins), = conj(H'[k]) / (|H'[k]|^2 + 1/snr_data) * e^{+j 2 pi d k / N} with d = tsr[1]: the
+ *     expression ofdm_rx_demod_frames builds its equaliser gains with, taken from H'.
+ *  6. A row without a sync is left exactly as it is -- no store to H' or gain -- and gets tail = +0.
+ * THE WINDOW IS THE CALLER'S CHOICE.  post must cover the channel's delay spread, pre the timing ambiguity of the sync: the search
+ * may lock onto a later path, and the earlier ones then sit at negative delays N - 1, N - 2, ...  On the two-path case of
+ * tests/csi_cases.py the search sometimes takes the second path (3 taps late) and a window with pre <= 2 cuts the first path off there
+ * and loses blocks that a window with pre >= 3 does not.  (cp/4, 3cp/4) is a reasonable start.
+ * WHAT tail IS.  The discarded taps hold noise only, so tail estimates the noise of the LS estimate per bin -- relative to the
+ * received preamble power, because the LS estimate is normalised by it: it reads about sigma^2 / (1 + sigma^2) for a signal of
+ * unit power in noise of variance sigma^2, plus a leakage term from the bins that are zero in H_ls (DC and the guard bands; about
+ * 0.014 at nfft 64, num_synch_bins 62).  It is not an absolute variance, but unlike the decision-directed estimates above it
+ * involves no symbol decisions and does not collapse at low SNR; per unit it serves as OFDM_MRC_NOISE_SEG input.  With wide
+ * guard bands (num_synch_bins well below nfft) the truncation also biases H' towards the band edges. */
+/* The stage on any device buffer: n_rows rows of nfft complex64 at d_H_in, d_tsr [n_rows][4] int32 ({., lag d, ., sync found} as
+ * ofdm_rx_demod_frames writes it).  d_H_out [n_rows][nfft] complex64 (d_H_out == d_H_in is allowed), d_gain_out
+ * [n_rows][num_data_bins] complex64 and d_tail [n_rows] float32 may be NULL.  One launch, asynchronous on `stream` (NULL = the
+ * handle's stream), no allocation.  OFDM_ERR_INVALID with the reason in ofdm_last_error(): pre < 0, post < 1, pre + post > nfft,
+ * n_rows negative or above 2^31 - 1, d_H_in, d_tsr or d_H_out missing.  n_rows == 0 is a no-op. */
+int ofdm_chan_window_frames(ofdm_rx* h, const float* d_H_in, const int32_t* d_tsr, int64_t n_rows, int32_t pre, int32_t post,
+                            float* d_H_out, float* d_gain_out, float* d_tail, void* stream);
+/* (0, 0) switches the stage off (the default); any other window must satisfy the rule above.  While it is on,
+ * ofdm_rx_demod_frames runs the stage in place on its channel estimates and gains between its sync and its demod launch (timed
+ * with the sync leg of ofdm_rx_set_profiling): d_eq, the hard bits, ofdm_rx_get_frame_state and ofdm_rx_csi_frames -- and with
+ * them every ofdm_rx_demod_frames_* call -- see the refined estimate.  While it is off that call issues exactly the launches it
+ * issued before.  The setting is read when ofdm_rx_demod_frames is called: a captured graph keeps the window it was captured
+ * with.  The stream block (ofdm_rx_work) is not affected. */
+int ofdm_rx_set_chan_window(ofdm_rx* h, int32_t pre, int32_t post);
+/* d_sigma2[f] = double(tail of frame f) of the LAST ofdm_rx_demod_frames call on this handle, f < n_frames: the layout
+ * OFDM_MRC_NOISE_SEG takes (frames of a branch-major batch are its units).  One launch, asynchronous on `stream`.
+ * OFDM_ERR_INVALID if the window was off in that call or n_frames exceeds its count. */
+int ofdm_rx_chan_noise_frames(ofdm_rx* h, int64_t n_frames, double* d_sigma2, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

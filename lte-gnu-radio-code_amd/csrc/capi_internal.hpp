@@ -84,6 +84,10 @@ struct ofdm_rx {
     cf* f_H = nullptr;
     cf* f_gain = nullptr;
     cf* f_htime = nullptr;
+    // ---- delay-window denoising of the channel estimate (ofdm_rx_set_chan_window): off while win_post == 0
+    int win_pre = 0, win_post = 0;
+    float* f_tail = nullptr;             // [cap_frames] tail power of the last windowed ofdm_rx_demod_frames call
+    int64_t tail_frames = -1;            // frames of the last ofdm_rx_demod_frames call if the window was on in it, else -1
     double* f_seg_partial = nullptr;     // [n_seg][seg_slices(seg_len)] sigma partials of ofdm_demap_frames
     int64_t cap_seg_partial = 0;
     // ---- pilot tracking stage (ofdm_rx_set_pilots): K = cfg.num_data_bins occupied bins, n_pilots of them pilots

@@ -532,6 +532,21 @@ hipError_t launch_fo_decide(const RxDev& rx, const FoDecideArgs& a, hipStream_t 
 hipError_t launch_fo_finalize(const RxDev& rx, const SyncArgs& a, int units_per_frame, hipStream_t s);
 // htime[r] = ifft(H[r]) for n_rows rows of nfft bins (est_chan_time on demand)
 hipError_t launch_rx_chan_time(const RxDev& rx, const cf* H, cf* htime, int n_rows, hipStream_t s);
+// delay-window denoising of LS channel estimates (rx_chanwin.hip): per row with tsr[3] == 1, H_out = fft(window(ifft(H_in))) on the
+// sync bins, the data-bin gains of sync_finalize from it, tail = N/M * the power of the M discarded taps.  One launch,
+// ceil(n_rows / SLOTS) workgroups.
+struct ChanWinArgs {
+    const cf* H_in;          // [n_rows][N]
+    const int* tsr;          // [n_rows][4]  {., lag, ., sync found}
+    int64_t n_rows;
+    int pre, post;           // taps kept: [0, post) and [N - pre, N)
+    cf* H_out;               // [n_rows][N]   may be H_in
+    cf* gain;                // [n_rows][Kd]  or null
+    float* tail;             // [n_rows]      or null
+};
+hipError_t launch_chan_window(const RxDev& rx, const ChanWinArgs& a, hipStream_t s);
+hipError_t launch_chan_noise(const float* tail, int64_t n, double* sigma2, hipStream_t s);   // sigma2[i] = double(tail[i])
+hipError_t chan_window_prepare();        // loads the kernels (before a stream capture)
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);
 // segmented soft de-mapper: pass 1 (nearest-point distance sums per slice) and pass 2 (sigma per segment + requested arrays)
 hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s);

@@ -425,6 +425,23 @@ class RxEngine(_Handle):
                                                            MRC_NOISE_GIVEN if given else MRC_NOISE_EST, nv, C.byref(out),
                                                            ptr(d_sigma2), ptr(stream))))
 
+    # ---- delay-window denoising of the LS channel estimate (include/ofdm_mi355x.h) ----------------------------------------------
+    def set_chan_window(self, pre: int, post: int):
+        """ofdm_rx_set_chan_window: while (pre, post) != (0, 0), demod_frames -- and every demod_frames_* call -- refines its
+        channel estimates by keeping the taps [0, post) and [nfft - pre, nfft) of their inverse FFT.  (0, 0) switches it off."""
+        check(self.lib.ofdm_rx_set_chan_window(self._h, int(pre), int(post)))
+
+    def chan_window_frames(self, d_H_in, d_tsr, n_rows, pre, post, d_H_out, d_gain_out=None, d_tail=None, stream=None):
+        """ofdm_chan_window_frames: the stage on n_rows rows of nfft complex64 at d_H_in with d_tsr [n_rows][4] int32.  Outputs
+        H' [n_rows][nfft] complex64 (may be d_H_in), gain [n_rows][Kd] complex64, tail [n_rows] float32."""
+        check(self.lib.ofdm_chan_window_frames(self._h, ptr(d_H_in), ptr(d_tsr), int(n_rows), int(pre), int(post), ptr(d_H_out),
+                                               ptr(d_gain_out), ptr(d_tail), ptr(stream)))
+
+    def chan_noise_frames(self, n_frames, d_sigma2, stream=None):
+        """ofdm_rx_chan_noise_frames: d_sigma2[f] (float64) = the tail power of frame f of the last demod_frames call, the per-unit
+        variances combine_csi_frames takes as d_sigma2."""
+        check(self.lib.ofdm_rx_chan_noise_frames(self._h, int(n_frames), ptr(d_sigma2), ptr(stream)))
+
     # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
     def reserve_tbcc(self, n_blocks: int, K: int):
         """Prepares decoding of up to n_blocks code blocks of K bits per call (before a graph capture)."""
