@@ -418,6 +418,72 @@ int ofdm_rx_set_chan_window(ofdm_rx* h, int32_t pre, int32_t post);
  * OFDM_ERR_INVALID if the window was off in that call or n_frames exceeds its count. */
 int ofdm_rx_chan_noise_frames(ofdm_rx* h, int64_t n_frames, double* d_sigma2, void* stream);
 
+/* ------------------------------------------------------------------------------------------ channel estimate averaged over every sync symbol of a frame
+ * An extension the reference does not have.  A frame holds n_pat = floor(floor(frame_len / L) / (S + D)) patterns (L = nfft + cp,
+ * S, D = synch_dat) and every pattern begins with a sync symbol; the batch receiver takes its LS estimate from the first one
+ * alone.  This stage takes one LS estimate per pattern, turns each onto the phase of the first and averages them: the time
+ * direction of channel estimation, where the delay window above is the frequency direction.  This text is the definition;
+ * tests/chanavg_ref.py restates it in fp64 NumPy.  The library computes in float32 with an FFT whose operation order is its own:
+ * it agrees with the definition to max|a - b| / max|b| < 1e-5 per output row, not bit for bit.
+ *
+ * Preconditions: synch_S == 1.  Every num_synch_bins the handle accepts is supported; num_synch_bins == nfft lists bin N/2
+ * twice, and as in the batch receiver's own estimate the bin keeps its last (positive-half) list entry while the power sum E_p
+ * counts both entries.  Every other sum over k below runs over the distinct sync bins.
+ *
+ * Per frame with a sync (tsr[3] == 1), t0 = tsr[0], lag d = tsr[1], N = nfft, SD = S + D, Ks = num_synch_bins.  n_avg >= 1 or -1
+ * (all); P = min(n_avg, n_pat) patterns p = 0 .. P - 1 are considered:
+ *  1. The window of pattern p starts at w_p = t0 + L * SD * p (64-bit): the CP-stripped sync symbol in front of the pattern's data.
+ *  2. It is a candidate iff 0 <= w_p and w_p + N <= frame_len: a sync symbol is never zero-padded.
+ *  3. Y_p = fft_N(x[w_p : w_p + N]); y_p = Y_p on binsP(num_synch_bins).
+ *  4. E_p = sum |y_p|^2.  The pattern takes part iff E_p is finite and > 0.
+ *  5. a_p[k] = sqrt(Ks / E_p) * y_p[k] * e^{+j 2 pi d k / N} * conj(zc[k]) / (1 + 1/snr_ls): for p = 0 the row
+ *     ofdm_rx_demod_frames writes without the stage.
+ *  Phase alignment.  c_p = sum_k a_p[k] conj(a_0[k]); u_p = c_p / |c_p| if |c_p| is finite and > 0, else the pattern does not
+ *  take part; u_0 = 1 + 0j.  (A carrier offset turns every later sync symbol by a common phase; the average stays referred to
+ *  pattern 0, the phase the demod kernel's gains assume.)
+ *  Mean.  n = the patterns that take part.  Pattern 0 always does for a frame the sync search accepted; if it does not (a
+ *  hostile d_tsr in the stand-alone call) the row is treated as a row without a sync.  d_p = conj(u_p) a_p - a_0;
+ *  Hbar = a_0 + (sum_p d_p) / n on the sync bins, +0 on every other bin.
+ *  Spread.  spread = (sum_p sum_k |d_p[k]|^2 - sum_k |sum_p d_p[k]|^2 / n) / ((n - 1) Ks) for n >= 2, +0 for n < 2: the per-bin
+ *  variance of ONE LS estimate about the frame's mean, relative to the received preamble power -- the units of the delay
+ *  window's tail without its leakage term, so it serves as OFDM_MRC_NOISE_SEG input.
+ *  Gains.  gain[j], j over binsP(num_data_bins), = conj(Hbar[k]) / (|Hbar[k]|^2 + 1/snr_data) * e^{+j 2 pi d k / N}.
+ *  Outputs per frame: Hbar [N] complex64, gain [num_data_bins] complex64, spread float32, n_used int32 = n, rot [P] complex64 =
+ *  u_p (+0+0j for a pattern that did not take part).  A row without a sync gets no store to Hbar or gain, spread = +0,
+ *  n_used = 0 and rot all +0.
+ *  Order of the sums.  Patterns are cut into chunks of OFDM_CHANAVG_CHUNK consecutive p.  Inside a chunk the sums over p run in
+ *  ascending p from +0 and a pattern that does not take part leaves them as they are; chunk sums are added in ascending chunk
+ *  order; sums over bins have a fixed order of their own.  The chunking depends on P and N alone: a frame gives the same bits
+ *  alone, in any batch and on every call.
+ * The angle of rot[p+1] * conj(rot[p]) divided by 2 pi SD L / N is the frame's carrier offset in subcarrier spacings; the stage
+ * does not correct it.  A channel that changes within a frame is what n_avg is for: the average covers the first n_avg patterns. */
+#define OFDM_CHANAVG_CHUNK 16
+/* The stage on any device IQ buffer: frame f at d_iq + 2 * f * frame_stride floats, d_tsr [n_frames][4] int32 as
+ * ofdm_rx_demod_frames writes it.  d_H_out [n_frames][nfft] complex64, d_gain_out [n_frames][num_data_bins] complex64, d_spread
+ * [n_frames] float32, d_n_used [n_frames] int32 and d_rot [n_frames][P] complex64 may each be NULL, but not all of them.  Two
+ * launches, asynchronous on `stream` (NULL = the handle's stream).  The chunk partials live in a workspace on the handle
+ * (ofdm_rx_reserve_chan_average); a call that needs a larger one grows it, which synchronises and is refused inside a stream
+ * capture.  OFDM_ERR_INVALID with the reason in ofdm_last_error(): null handle, synch_S != 1, n_avg of 0 or below -1, negative
+ * counts, n_frames above 2^31 - 1, frame_stride < frame_len, d_iq or d_tsr missing, no output wanted.  n_frames == 0 is a no-op. */
+int ofdm_chan_average_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                             const int32_t* d_tsr, int32_t n_avg, float* d_H_out, float* d_gain_out, float* d_spread,
+                             int32_t* d_n_used, float* d_rot, void* stream);
+/* 0 switches the stage off (the default); n_avg >= 1 or -1 (all patterns) switches it on, below -1 is OFDM_ERR_INVALID and so is
+ * switching it on with synch_S != 1.  While it is on, ofdm_rx_demod_frames runs the stage in place on its channel estimates and
+ * gains between its sync launch and the delay window (timed with the sync leg of ofdm_rx_set_profiling): d_eq, the hard bits,
+ * ofdm_rx_get_frame_state, ofdm_rx_csi_frames, the delay window -- and with them every ofdm_rx_demod_frames_* call -- see the
+ * averaged estimate.  While it is off that call issues exactly the launches it issued before.  The setting is read when
+ * ofdm_rx_demod_frames is called: a captured graph keeps the setting it was captured with.  The stream block (ofdm_rx_work), the
+ * CFO receiver and the tracker are not affected. */
+int ofdm_rx_set_chan_average(ofdm_rx* h, int32_t n_avg);
+/* Workspace for the chunk partials of n_frames frames of frame_len samples (all patterns), outside a stream capture; never
+ * shrinks.  With ofdm_rx_reserve before it, a first averaged ofdm_rx_demod_frames inside a capture has nothing left to set up. */
+int ofdm_rx_reserve_chan_average(ofdm_rx* h, int64_t n_frames, int64_t frame_len);
+/* d_sigma2[f] = double(spread of frame f) of the LAST ofdm_rx_demod_frames call on this handle, f < n_frames: the layout
+ * OFDM_MRC_NOISE_SEG takes.  One launch, asynchronous on `stream`.  OFDM_ERR_INVALID if the stage was off in that call or
+ * n_frames exceeds its count. */
+int ofdm_rx_chan_spread_frames(ofdm_rx* h, int64_t n_frames, double* d_sigma2, void* stream);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

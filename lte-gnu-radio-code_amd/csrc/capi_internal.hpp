@@ -31,6 +31,8 @@ std::vector<cf> make_zc(int mm, int root, int parity_of);
 std::vector<cf> make_scan_table(int N, int Ks, const std::vector<cf>& zc);
 int fill_rxdev(const ofdm_rx_cfg& cfg, RxDev& d);                      // derived constants; returns the Zadoff-Chu root
 int upload_rx_tables(RxDev& d, cf** d_tw, cf** d_zc, const std::vector<cf>& zc);
+// capi_chanavg.hip: the averaging stage of ofdm_rx_demod_frames, in place on the rows its sync launch just wrote
+int chan_average_in_place(ofdm_rx* h, const cf* iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len, hipStream_t s);
 #pragma GCC visibility pop
 
 #define HIP_TRY(expr)                                                                              \
@@ -88,6 +90,15 @@ struct ofdm_rx {
     int win_pre = 0, win_post = 0;
     float* f_tail = nullptr;             // [cap_frames] tail power of the last windowed ofdm_rx_demod_frames call
     int64_t tail_frames = -1;            // frames of the last ofdm_rx_demod_frames call if the window was on in it, else -1
+    // ---- channel estimate averaged over the sync symbols of a frame (ofdm_rx_set_chan_average): off while avg_n == 0
+    int avg_n = 0;                       // patterns averaged (-1 = all of a frame)
+    float* f_spread = nullptr;           // [cap_frames] spread of the last averaged ofdm_rx_demod_frames call
+    int64_t spread_frames = -1;          // frames of the last ofdm_rx_demod_frames call if the stage was on in it, else -1
+    cf* a_part_d = nullptr;              // [frames][chunks][N] chunk partials (ChanAvgArgs)
+    cf* a_part_a0 = nullptr;             // [frames][N]
+    float* a_part_q = nullptr;           // [frames][chunks]
+    int* a_part_n = nullptr;             // [frames][chunks]
+    int64_t cap_avg_frames = 0, cap_avg_items = 0;   // frames, frames * chunks
     double* f_seg_partial = nullptr;     // [n_seg][seg_slices(seg_len)] sigma partials of ofdm_demap_frames
     int64_t cap_seg_partial = 0;
     // ---- pilot tracking stage (ofdm_rx_set_pilots): K = cfg.num_data_bins occupied bins, n_pilots of them pilots

@@ -17,7 +17,7 @@ int ofdm_rx_destroy(ofdm_rx* h) {
     free_dev(&h->tb_ws, &h->d_pack, &h->d_tw, &h->d_zc, &h->d_in, &h->d_edf, &h->s_tsr, &h->s_H, &h->s_htime, &h->s_esf, &h->s_eqg, &h->s_gain,
              &h->s_ysc, &h->d_trial_m, &h->d_trial_d, &h->d_partial, &h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime, &h->d_scan_g,
              &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws, &h->c_part_e,
-             &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail);
+             &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail, &h->f_spread, &h->a_part_d, &h->a_part_a0, &h->a_part_q, &h->a_part_n);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -163,9 +163,11 @@ int ofdm_rx_reserve(ofdm_rx* h, int64_t n_frames) {
     if (n_frames <= h->cap_frames) return OFDM_OK;
     h->last_frames = 0;                  // the rows of f_H go with the old buffer: none until the next ofdm_rx_demod_frames
     h->tail_frames = -1;                 // ... and so do the tail powers
+    h->spread_frames = -1;               // ... and the spreads
     return regrow(h, {{&h->cap_frames, n_frames}}, ws_buf(&h->f_tsr, size_t(n_frames) * 4),
                   ws_buf(&h->f_H, size_t(n_frames) * h->dev.nfft), ws_buf(&h->f_gain, size_t(n_frames) * h->dev.Kd),
-                  ws_buf(&h->f_htime, size_t(n_frames) * h->dev.nfft), ws_buf(&h->f_tail, size_t(n_frames)));
+                  ws_buf(&h->f_htime, size_t(n_frames) * h->dev.nfft), ws_buf(&h->f_tail, size_t(n_frames)),
+                  ws_buf(&h->f_spread, size_t(n_frames)));
 }
 
 int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride,
@@ -212,6 +214,11 @@ int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, in
     HIP_TRY(launch_rx_sync(d, sa, s));
     h->last_frames = n_frames;           // rows of f_H this call wrote (ofdm_rx_csi_frames)
     h->tail_frames = -1;
+    h->spread_frames = -1;
+    if (h->avg_n != 0) {                 // the estimate averaged over the frame's sync symbols, in place (capi_chanavg.hip)
+        const int rc = chan_average_in_place(h, sa.iq, n_frames, frame_stride, frame_len, s);
+        if (rc != OFDM_OK) return rc;
+    }
     if (h->win_post > 0) {               // delay-window denoising, in place on the rows the sync launch just wrote (capi_chanwin.hip)
         ChanWinArgs wa{};
         wa.H_in = h->f_H;

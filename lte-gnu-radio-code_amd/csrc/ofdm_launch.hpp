@@ -547,6 +547,33 @@ struct ChanWinArgs {
 hipError_t launch_chan_window(const RxDev& rx, const ChanWinArgs& a, hipStream_t s);
 hipError_t launch_chan_noise(const float* tail, int64_t n, double* sigma2, hipStream_t s);   // sigma2[i] = double(tail[i])
 hipError_t chan_window_prepare();        // loads the kernels (before a stream capture)
+// channel estimate averaged over the sync symbols of a frame (rx_chanavg.hip; contract: include/ofdm_mi355x.h, "channel estimate
+// averaged over every sync symbol of a frame").  Two launches: chan_avg_kernel<N>, one work item per (frame, chunk of
+// CHANAVG_CHUNK patterns), leaves one partial per item in the workspace and the rotations in rot; chan_avg_finalize_kernel adds a
+// frame's partials in chunk order and writes the outputs that are not null.
+constexpr int CHANAVG_CHUNK = 16;
+inline int64_t chanavg_chunks(int64_t n_pat) { return (n_pat + CHANAVG_CHUNK - 1) / CHANAVG_CHUNK; }
+struct ChanAvgArgs {
+    const cf* iq;            // frames, frame f at iq + f*frame_stride
+    int64_t frame_stride;
+    int64_t frame_len;
+    int64_t n_frames;
+    const int* tsr;          // [n_frames][4]  {t0, lag, ., sync found}
+    int n_pat;               // P: patterns considered per frame, min(n_avg, patterns of a frame)
+    int n_chunks;            // chanavg_chunks(n_pat)
+    cf* part_d;              // workspace [n_frames][n_chunks][N]: the chunk's sum of d_p on the sync bins
+    cf* part_a0;             // workspace [n_frames][N]: a_0 on the sync bins (written by chunk 0)
+    float* part_q;           // workspace [n_frames][n_chunks]: the chunk's sum of |d_p|^2
+    int* part_n;             // workspace [n_frames][n_chunks]: patterns of the chunk that take part
+    cf* H_out;               // [n_frames][N]      or null
+    cf* gain;                // [n_frames][Kd]     or null
+    float* spread;           // [n_frames]         or null
+    int* n_used;             // [n_frames]         or null
+    cf* rot;                 // [n_frames][n_pat]  or null
+};
+hipError_t launch_chan_average(const RxDev& rx, const ChanAvgArgs& a, hipStream_t s);
+hipError_t launch_chan_spread(const float* spread, int64_t n, double* sigma2, hipStream_t s);   // sigma2[i] = double(spread[i])
+hipError_t chan_average_prepare();       // loads the kernels (before a stream capture)
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);
 // segmented soft de-mapper: pass 1 (nearest-point distance sums per slice) and pass 2 (sigma per segment + requested arrays)
 hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s);

@@ -196,6 +196,11 @@ PROTOTYPES = {
                                           C.c_void_p, C.c_void_p]),
     "ofdm_rx_set_chan_window": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "ofdm_rx_chan_noise_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ofdm_chan_average_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ofdm_rx_set_chan_average": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ofdm_rx_reserve_chan_average": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "ofdm_rx_chan_spread_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ofdm_rx_reserve_mrc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
     "ofdm_combine_csi_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,

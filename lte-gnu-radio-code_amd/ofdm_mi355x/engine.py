@@ -442,6 +442,33 @@ class RxEngine(_Handle):
         variances combine_csi_frames takes as d_sigma2."""
         check(self.lib.ofdm_rx_chan_noise_frames(self._h, int(n_frames), ptr(d_sigma2), ptr(stream)))
 
+    # ---- channel estimate averaged over every sync symbol of a frame (include/ofdm_mi355x.h) ------------------------------------
+    CHANAVG_CHUNK = 16               # OFDM_CHANAVG_CHUNK: consecutive patterns whose sums one work item forms
+
+    def set_chan_average(self, n_avg: int):
+        """ofdm_rx_set_chan_average: while n_avg != 0, demod_frames -- and every demod_frames_* call -- replaces its channel
+        estimates by the phase-aligned mean of the LS estimates of the first n_avg sync symbols of each frame (-1 = all of them),
+        ahead of the delay window.  0 switches it off.  Needs synch_dat[0] == 1."""
+        check(self.lib.ofdm_rx_set_chan_average(self._h, int(n_avg)))
+
+    def reserve_chan_average(self, n_frames: int, frame_len: int):
+        """ofdm_rx_reserve_chan_average: workspace for averaging n_frames frames of frame_len samples (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_chan_average(self._h, int(n_frames), int(frame_len)))
+
+    def chan_average_frames(self, d_iq, n_frames, frame_stride, frame_len, d_tsr, n_avg, d_H_out=None, d_gain_out=None,
+                            d_spread=None, d_n_used=None, d_rot=None, stream=None):
+        """ofdm_chan_average_frames: the stage on any device IQ buffer with d_tsr [n_frames][4] int32.  Outputs, each optional but
+        not all: Hbar [n_frames][nfft] complex64, gain [n_frames][Kd] complex64, spread [n_frames] float32, n_used [n_frames]
+        int32, rot [n_frames][P] complex64 with P = min(n_avg, patterns per frame)."""
+        check(self.lib.ofdm_chan_average_frames(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len), ptr(d_tsr),
+                                                int(n_avg), ptr(d_H_out), ptr(d_gain_out), ptr(d_spread), ptr(d_n_used), ptr(d_rot),
+                                                ptr(stream)))
+
+    def chan_spread_frames(self, n_frames, d_sigma2, stream=None):
+        """ofdm_rx_chan_spread_frames: d_sigma2[f] (float64) = the spread of frame f of the last demod_frames call, the per-unit
+        variances combine_csi_frames takes as d_sigma2."""
+        check(self.lib.ofdm_rx_chan_spread_frames(self._h, int(n_frames), ptr(d_sigma2), ptr(stream)))
+
     # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
     def reserve_tbcc(self, n_blocks: int, K: int):
         """Prepares decoding of up to n_blocks code blocks of K bits per call (before a graph capture)."""
