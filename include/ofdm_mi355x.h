@@ -484,6 +484,85 @@ int ofdm_rx_reserve_chan_average(ofdm_rx* h, int64_t n_frames, int64_t frame_len
  * n_frames exceeds its count. */
 int ofdm_rx_chan_spread_frames(ofdm_rx* h, int64_t n_frames, double* d_sigma2, void* stream);
 
+/* ------------------------------------------------------------------------------------------ channel tracked across the sync symbols of a frame
+ * An extension the reference does not have.  The batch receiver equalises every data symbol of a frame with ONE channel estimate;
+ * the delay window and the average above refine that one estimate and assume with it that the channel stands still for the whole
+ * frame.  This stage drops the assumption: it takes one LS estimate per sync symbol and equalises every data symbol with an
+ * estimate interpolated in time between the sync symbols around it.  This text is the definition; tests/chantrack_ref.py restates
+ * it in fp64 NumPy.  The library computes in float32 with an FFT whose operation order is its own: it agrees with the definition
+ * to max|a - b| / max|b| < 1e-5 per output row, not bit for bit.
+ *
+ * Precondition: synch_S == 1.  Every num_synch_bins / num_data_bins pair the handle accepts is supported; num_synch_bins == nfft
+ * lists bin N/2 twice, with the rule the averaging section states (and so does num_data_bins == nfft: P_s counts both entries
+ * and both list entries of the output row hold the bin's value).
+ *
+ * N = nfft, L = N + cp, SD = S + D, Ks = num_synch_bins, Kd = num_data_bins.  Per frame with a sync (tsr[3] == 1), t0 = tsr[0],
+ * lag d = tsr[1], n_pat = floor(floor(frame_len / L) / SD) patterns:
+ *  1. Per-pattern estimates.  For every p < n_pat, a_p is formed exactly as in steps 1-5 of the averaging section: the window
+ *     starts at w_p = t0 + L * SD * p, is a candidate iff 0 <= w_p and w_p + N <= frame_len (never zero-padded), E_p is summed
+ *     over the sync-bin list, the pattern TAKES PART iff E_p is finite and > 0, and
+ *     a_p[k] = sqrt(Ks / E_p) * y_p[k] * e^{+j 2 pi d k / N} * conj(zc[k]) / (1 + 1/snr_ls) on the sync bins, +0 elsewhere.
+ *     There is NO phase alignment: the estimates keep their own phase, and following it is the point of the stage.  If pattern 0
+ *     does not take part the frame is treated as a frame without a sync.
+ *  2. Optional delay window.  With a window (pre, post) != (0, 0), every a_p that takes part is replaced by H' of steps 1-4 of
+ *     the delay-window section applied to that row; (0, 0) means off; the rule for valid windows is that section's.
+ *  3. Neighbours and weight.  Data symbol m (0 <= m < D) of pattern p has the symbol index s = p * SD + S + m.  lo = the largest
+ *     q <= p that takes part (pattern 0 does); hi = the smallest q > p that takes part, if there is one.
+ *     OFDM_TRACK_LINEAR: w = float32(s - lo * SD) / float32((hi - lo) * SD), H = a_lo + w (a_hi - a_lo); without a hi H = a_lo
+ *     (no extrapolation past the last sync symbol).  OFDM_TRACK_HOLD: H = a_lo always.
+ *  4. Demodulation, with the windows and the guard of ofdm_rx_demod_frames: ptr_p = t0 + L * (p * SD + 1); pattern p is
+ *     demodulated iff ptr_p + N - 1 <= frame_len, otherwise its D rows are zeros.  Symbol m starts at ptr_p + L * m, samples
+ *     outside [0, frame_len) read as zero like fft(x, N); Y = fft_N; P_s = sum |Y[k]|^2 over the list binsP(Kd);
+ *     z_j = Y[k] * sqrt(Kd / P_s) * conj(H[k]) / (|H[k]|^2 + 1/snr_data) * e^{+j 2 pi d k / N}, j over binsP(Kd) in list order.
+ *     A non-finite or zero P_s gives what IEEE arithmetic of these formulas gives.
+ *  5. Outputs per frame, each optional but not all:
+ *       eq    [n_pat*D][Kd] complex64
+ *       bits  the hard decision, by the rules of ofdm_demap, of the STORED float32 eq values, zero rows included; modulation =
+ *             cfg.modulation; packed MSB-first [n_pat*D*Kd*bps/8] bytes or one bit per byte
+ *       csi   [n_pat*D][Kd] float32 = re*re + im*im of H[k] (each product rounded) for EVERY data symbol of the frame, whether
+ *             its pattern is demodulated or not: ofdm_demap_csi_frames with one ROW per segment (n_seg = n_frames*n_pat*D,
+ *             rows = 1, csi_stride = Kd) weighs every symbol with its own channel power
+ *       H_pat [n_pat][N] complex64 = a_p after step 2, +0 rows for patterns that do not take part
+ *       takes [n_pat] int32, 1 or 0
+ *     A frame without a sync gets zero rows in eq, the bits of zeros, +0 in csi and H_pat and 0 in takes.
+ *  6. Every symbol is computed on its own in a fixed order: a frame gives the same bits alone, in any batch, at any buffer
+ *     alignment and on every call. */
+typedef enum { OFDM_TRACK_HOLD = 0, OFDM_TRACK_LINEAR = 1 } ofdm_track_mode;
+typedef struct ofdm_track_out {      /* DEVICE pointers; NULL = not wanted */
+    float*   eq;
+    uint8_t* bits;
+    float*   csi;
+    float*   H_pat;
+    int32_t* takes;
+} ofdm_track_out;
+/* The stage on any device IQ buffer: frame f at d_iq + 2 * f * frame_stride floats, d_tsr [n_frames][4] int32 as
+ * ofdm_rx_demod_frames writes it.  Asynchronous on `stream` (NULL = the handle's stream): the estimate launch, a small launch
+ * that links every pattern to its neighbours, the delay-window launch over the n_frames * n_pat rows if a window is given, the
+ * demod launch if eq, bits or csi is wanted and a hard-decision launch over the stored rows if bits is.  The flags, the
+ * neighbours and -- for a call that does not take H_pat -- the rows a_p live in a workspace on the handle
+ * (ofdm_rx_reserve_chan_track); a call that needs a larger one grows it, which synchronises and is refused inside a stream
+ * capture, before anything is enqueued.  bits without eq keeps the equalised rows in a second workspace that grows on demand
+ * only, outside a capture.  Returns n_pat*D or a negative status.  OFDM_ERR_INVALID with the reason in
+ * ofdm_last_error(), before anything is enqueued: null handle, synch_S != 1, an unknown mode, a window that is neither (0, 0)
+ * nor valid, an unknown bits_mode, bits wanted with OFDM_BITS_NONE (or packed bits the numerology cannot pack), negative counts,
+ * frame_stride < frame_len, a batch beyond the kernels' index range, d_iq or d_tsr missing, an `out` without any pointer.
+ * n_frames == 0 is a no-op that returns the row count. */
+int64_t ofdm_chan_track_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                               const int32_t* d_tsr, int32_t mode, int32_t pre, int32_t post, int32_t bits_mode,
+                               const ofdm_track_out* out, void* stream);
+/* The sync search of ofdm_rx_demod_frames (the same d_tsr bits; d_tsr may be NULL), then the stage with the window of
+ * ofdm_rx_set_chan_window.  The call runs the handle's sync launch ONLY: the averaging setting (ofdm_rx_set_chan_average) is
+ * not applied here -- it is the opposite assumption -- and the handle's per-frame state (ofdm_rx_get_frame_state,
+ * ofdm_rx_csi_frames) stays as the sync launch wrote it, without the window.  The window and the mode are read when the call is
+ * made: a captured graph keeps them.  Refusals as above. */
+int64_t ofdm_rx_demod_frames_track(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                   int32_t mode, int32_t bits_mode, int32_t* d_tsr, const ofdm_track_out* out, void* stream);
+/* Workspace of the stage for n_frames frames of frame_len samples (n_frames * n_pat rows of nfft complex64, the flags, the
+ * neighbours and the row tsr of the window launch: what a call without H_pat needs; a call that takes H_pat allocates no rows
+ * of its own), outside a stream capture; never shrinks; loads the kernels.  With
+ * ofdm_rx_reserve before it, a first ofdm_rx_demod_frames_track inside a capture has nothing left to set up. */
+int ofdm_rx_reserve_chan_track(ofdm_rx* h, int64_t n_frames, int64_t frame_len);
+
 /* ------------------------------------------------------------------------------------------ TX
  * Replaces MultiAntennaSystem.multi_ant_binary_map + multi_ant_symb_gen (single antenna)
  * (G/LEGACY/gr-ofdm-rx/python/txrx_mod/MultiAntennaSystem.py:113-218) and SynchSignal (:13-30). */

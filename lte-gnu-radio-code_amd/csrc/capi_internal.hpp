@@ -33,6 +33,9 @@ int fill_rxdev(const ofdm_rx_cfg& cfg, RxDev& d);                      // derive
 int upload_rx_tables(RxDev& d, cf** d_tw, cf** d_zc, const std::vector<cf>& zc);
 // capi_chanavg.hip: the averaging stage of ofdm_rx_demod_frames, in place on the rows its sync launch just wrote
 int chan_average_in_place(ofdm_rx* h, const cf* iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len, hipStream_t s);
+// capi_rx.hip: the sync leg of ofdm_rx_demod_frames alone -- its search launch into the handle's per-frame state (the workspace
+// covers n_frames)
+int rx_sync_leg(ofdm_rx* h, const cf* iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len, hipStream_t s);
 #pragma GCC visibility pop
 
 #define HIP_TRY(expr)                                                                              \
@@ -99,6 +102,15 @@ struct ofdm_rx {
     float* a_part_q = nullptr;           // [frames][chunks]
     int* a_part_n = nullptr;             // [frames][chunks]
     int64_t cap_avg_frames = 0, cap_avg_items = 0;   // frames, frames * chunks
+    // ---- channel tracked across the sync symbols of a frame (ofdm_rx_reserve_chan_track)
+    cf* k_H = nullptr;                   // [frames][n_pat][N] a_p when the caller does not take H_pat (ChanTrackArgs)
+    int64_t cap_trk_H = 0;               // rows of k_H: grown by the reserve call and by calls without H_pat only
+    int* k_flag = nullptr;               // [frames][n_pat]
+    int2* k_nb = nullptr;                // [frames][n_pat] {lo, hi}
+    int* k_rtsr = nullptr;               // [frames][n_pat][4] row tsr of the delay-window launch
+    int64_t cap_trk_rows = 0;            // frames * n_pat
+    cf* k_eq = nullptr;                  // equalised rows of a call that wants bits without eq
+    int64_t cap_trk_eq = 0;              // symbols
     double* f_seg_partial = nullptr;     // [n_seg][seg_slices(seg_len)] sigma partials of ofdm_demap_frames
     int64_t cap_seg_partial = 0;
     // ---- pilot tracking stage (ofdm_rx_set_pilots): K = cfg.num_data_bins occupied bins, n_pilots of them pilots
@@ -305,9 +317,12 @@ int regrow(H* h, std::initializer_list<WsCap> caps, WsBuf<T>... bufs) {
 }
 
 // a workspace that must grow cannot do so inside a stream capture (growing synchronises and allocates)
-int refuse_growth_in_capture(hipStream_t s, const char* who, const char* reserve_name) {
+bool stream_is_capturing(hipStream_t s) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+int refuse_growth_in_capture(hipStream_t s, const char* who, const char* reserve_name) {
+    if (stream_is_capturing(s))
         return fail(OFDM_ERR_INVALID, "%s: workspace must grow, which cannot happen inside a capture (call %s first)", who, reserve_name);
     return OFDM_OK;
 }

@@ -17,7 +17,8 @@ int ofdm_rx_destroy(ofdm_rx* h) {
     free_dev(&h->tb_ws, &h->d_pack, &h->d_tw, &h->d_zc, &h->d_in, &h->d_edf, &h->s_tsr, &h->s_H, &h->s_htime, &h->s_esf, &h->s_eqg, &h->s_gain,
              &h->s_ysc, &h->d_trial_m, &h->d_trial_d, &h->d_partial, &h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime, &h->d_scan_g,
              &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws, &h->c_part_e,
-             &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail, &h->f_spread, &h->a_part_d, &h->a_part_a0, &h->a_part_q, &h->a_part_n);
+             &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail, &h->f_spread, &h->a_part_d, &h->a_part_a0, &h->a_part_q, &h->a_part_n,
+             &h->k_H, &h->k_flag, &h->k_nb, &h->k_rtsr, &h->k_eq);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);
@@ -170,6 +171,37 @@ int ofdm_rx_reserve(ofdm_rx* h, int64_t n_frames) {
                   ws_buf(&h->f_spread, size_t(n_frames)));
 }
 
+}  // extern "C"
+
+int rx_sync_leg(ofdm_rx* h, const cf* iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len, hipStream_t s) {
+    SyncArgs sa{};
+    sa.iq = iq;
+    sa.frame_stride = frame_stride;
+    sa.frame_len = frame_len;
+    sa.n_frames = int(n_frames);
+    sa.mode = 0;
+    sa.p_begin = 0;
+    sa.p_count = h->max_trials;
+    sa.force_accept = 0;
+    sa.tsr = h->f_tsr;
+    sa.H = h->f_H;
+    sa.H_for_gain = nullptr;
+    sa.gain = h->f_gain;
+    sa.htime = nullptr;                  // est_chan_time is computed on demand (ofdm_rx_get_frame_state)
+    sa.scan_block = h->scan_block;       // screened search where its preconditions hold (same outcome as the exhaustive one)
+    sa.scan_g = h->d_scan_g;
+#ifdef OFDM_EXPERIMENTS
+    sa.stamps = h->d_stamps;
+#endif
+    HIP_TRY(launch_rx_sync(h->dev, sa, s));
+    h->last_frames = n_frames;           // rows of f_H this call wrote (ofdm_rx_csi_frames)
+    h->tail_frames = -1;
+    h->spread_frames = -1;
+    return OFDM_OK;
+}
+
+extern "C" {
+
 int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride,
                              int64_t frame_len, float* d_eq, uint8_t* d_bits, int32_t bits_mode, int32_t* d_tsr,
                              void* stream) {
@@ -190,33 +222,12 @@ int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, in
     }
     hipStream_t s = pick_stream(h, stream);
 
-    SyncArgs sa{};
-    sa.iq = reinterpret_cast<const cf*>(d_iq);
-    sa.frame_stride = frame_stride;
-    sa.frame_len = frame_len;
-    sa.n_frames = int(n_frames);
-    sa.mode = 0;
-    sa.p_begin = 0;
-    sa.p_count = h->max_trials;
-    sa.force_accept = 0;
-    sa.tsr = h->f_tsr;
-    sa.H = h->f_H;
-    sa.H_for_gain = nullptr;
-    sa.gain = h->f_gain;
-    sa.htime = nullptr;                  // est_chan_time is computed on demand (ofdm_rx_get_frame_state)
-    sa.scan_block = h->scan_block;       // screened search where its preconditions hold (same outcome as the exhaustive one)
-    sa.scan_g = h->d_scan_g;
-#ifdef OFDM_EXPERIMENTS
-    sa.stamps = h->d_stamps;
-#endif
+    const cf* iq = reinterpret_cast<const cf*>(d_iq);
     hipEvent_t* pev = h->ev + 3 * (h->prof_calls % ofdm_rx::PROF_RING);
     if (h->profiling) HIP_TRY(hipEventRecord(pev[0], s));
-    HIP_TRY(launch_rx_sync(d, sa, s));
-    h->last_frames = n_frames;           // rows of f_H this call wrote (ofdm_rx_csi_frames)
-    h->tail_frames = -1;
-    h->spread_frames = -1;
+    if (const int rc = rx_sync_leg(h, iq, n_frames, frame_stride, frame_len, s)) return rc;
     if (h->avg_n != 0) {                 // the estimate averaged over the frame's sync symbols, in place (capi_chanavg.hip)
-        const int rc = chan_average_in_place(h, sa.iq, n_frames, frame_stride, frame_len, s);
+        const int rc = chan_average_in_place(h, iq, n_frames, frame_stride, frame_len, s);
         if (rc != OFDM_OK) return rc;
     }
     if (h->win_post > 0) {               // delay-window denoising, in place on the rows the sync launch just wrote (capi_chanwin.hip)
@@ -236,7 +247,7 @@ int64_t ofdm_rx_demod_frames(ofdm_rx* h, const float* d_iq, int64_t n_frames, in
 
     if (n_dsym > 0 && (d_eq || d_bits)) {
         DemodArgs da{};
-        da.iq = sa.iq;
+        da.iq = iq;
         da.frame_stride = frame_stride;
         da.frame_len = frame_len;
         da.n_frames = int(n_frames);

@@ -574,6 +574,38 @@ struct ChanAvgArgs {
 hipError_t launch_chan_average(const RxDev& rx, const ChanAvgArgs& a, hipStream_t s);
 hipError_t launch_chan_spread(const float* spread, int64_t n, double* sigma2, hipStream_t s);   // sigma2[i] = double(spread[i])
 hipError_t chan_average_prepare();       // loads the kernels (before a stream capture)
+// channel tracked across the sync symbols of a frame (rx_chantrack.hip; contract: include/ofdm_mi355x.h, "channel tracked across
+// the sync symbols of a frame").  launch_chan_track_est: chan_track_est_kernel<N>, one work item per (frame, pattern), writes the
+// row a_p and the pattern's flag; chan_track_link_kernel, one workgroup per frame, turns the flags into the neighbours {lo, hi}
+// of every pattern, the `takes` output and the row tsr of the delay window.  The caller may run launch_chan_window over the
+// n_frames * n_pat rows in between.  launch_chan_track_demod: rx_demod_track_kernel<N>, one work item per (frame, run of
+// CHANTRACK_RUN consecutive data symbols), then (bits != null) the hard-decision pass over the stored rows.
+constexpr int CHANTRACK_RUN = 12;
+inline int64_t chantrack_runs(int64_t n_dsym) { return (n_dsym + CHANTRACK_RUN - 1) / CHANTRACK_RUN; }
+struct ChanTrackArgs {
+    const cf* iq;            // frames, frame f at iq + f*frame_stride
+    int64_t frame_stride;
+    int64_t frame_len;
+    int64_t n_frames;
+    const int* tsr;          // [n_frames][4]  {t0, lag, ., sync found}
+    int n_pat;               // patterns per frame
+    int n_dsym;              // n_pat * D
+    int n_runs;              // chantrack_runs(n_dsym)
+    int linear;              // 1: OFDM_TRACK_LINEAR, 0: OFDM_TRACK_HOLD
+    cf* H_pat;               // [n_frames][n_pat][N]: a_p (the caller's buffer or the workspace)
+    int* flag;               // workspace [n_frames][n_pat]: the pattern takes part
+    int2* nb;                // workspace [n_frames][n_pat]: {lo, hi or -1}
+    int* row_tsr;            // workspace [n_frames][n_pat][4] {0, lag, 0, takes} for launch_chan_window, or null
+    int* takes;              // [n_frames][n_pat] or null
+    cf* eq;                  // [n_frames][n_dsym][Kd]: the caller's buffer, the workspace (bits alone) or null
+    float* csi;              // [n_frames][n_dsym][Kd] or null
+    uint8_t* bits;           // hard bits of eq, or null
+    int bits_mode;           // ofdm_bits_mode
+    int mod;                 // bits per symbol (1, 2, 4, 6)
+};
+hipError_t launch_chan_track_est(const RxDev& rx, const ChanTrackArgs& a, hipStream_t s);
+hipError_t launch_chan_track_demod(const RxDev& rx, const ChanTrackArgs& a, hipStream_t s);
+hipError_t chan_track_prepare();         // loads the kernels (before a stream capture)
 hipError_t launch_demap(const DemapArgs& a, hipStream_t s);
 // segmented soft de-mapper: pass 1 (nearest-point distance sums per slice) and pass 2 (sigma per segment + requested arrays)
 hipError_t launch_demap_frames(const SegDemapArgs& a, hipStream_t s);

@@ -28,6 +28,7 @@ CSI_NOISE_EST, CSI_NOISE_GIVEN = 0, 1
 CSI_ROWS_ALL, CSI_ROWS_DATA = 0, 1
 MRC_NOISE_GIVEN, MRC_NOISE_SEG, MRC_NOISE_EST = 0, 1, 2
 MRC_MAX_BRANCHES = 8
+TRACK_HOLD, TRACK_LINEAR = 0, 1
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -95,6 +96,11 @@ class CsiOut(C.Structure):
 class MrcOut(C.Structure):
     """ofdm_mrc_out: device pointers of the receive-diversity combiner (None = not wanted)."""
     _fields_ = [("llr", C.c_void_p), ("sym", C.c_void_p), ("weight", C.c_void_p)]
+
+
+class TrackOut(C.Structure):
+    """ofdm_track_out: device pointers of the channel-tracking stage (None = not wanted)."""
+    _fields_ = [("eq", C.c_void_p), ("bits", C.c_void_p), ("csi", C.c_void_p), ("H_pat", C.c_void_p), ("takes", C.c_void_p)]
 
 
 class TbccOut(C.Structure):
@@ -201,6 +207,11 @@ PROTOTYPES = {
     "ofdm_rx_set_chan_average": (C.c_int, [C.c_void_p, C.c_int32]),
     "ofdm_rx_reserve_chan_average": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "ofdm_rx_chan_spread_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ofdm_chan_track_frames": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.POINTER(TrackOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_track": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                               C.c_void_p, C.POINTER(TrackOut), C.c_void_p]),
+    "ofdm_rx_reserve_chan_track": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "ofdm_rx_reserve_mrc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64]),
     "ofdm_combine_csi_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_int64, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,

@@ -469,6 +469,36 @@ class RxEngine(_Handle):
         variances combine_csi_frames takes as d_sigma2."""
         check(self.lib.ofdm_rx_chan_spread_frames(self._h, int(n_frames), ptr(d_sigma2), ptr(stream)))
 
+    # ---- channel tracked across the sync symbols of a frame (include/ofdm_mi355x.h) ---------------------------------------------
+    TRACK_HOLD, TRACK_LINEAR = _lib.TRACK_HOLD, _lib.TRACK_LINEAR
+
+    @staticmethod
+    def _track_out(d_eq, d_bits, d_csi, d_H_pat, d_takes):
+        return _lib.TrackOut(_addr(d_eq), _addr(d_bits), _addr(d_csi), _addr(d_H_pat), _addr(d_takes))
+
+    def reserve_chan_track(self, n_frames: int, frame_len: int):
+        """ofdm_rx_reserve_chan_track: workspace for tracking n_frames frames of frame_len samples (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_chan_track(self._h, int(n_frames), int(frame_len)))
+
+    def chan_track_frames(self, d_iq, n_frames, frame_stride, frame_len, d_tsr, mode=_lib.TRACK_LINEAR, pre=0, post=0, d_eq=None,
+                          d_bits=None, bits_mode=BITS_NONE, d_csi=None, d_H_pat=None, d_takes=None, stream=None) -> int:
+        """ofdm_chan_track_frames: one LS estimate per sync symbol of every frame and every data symbol equalised with the estimate
+        interpolated (TRACK_LINEAR) or held (TRACK_HOLD) between them; (pre, post) != (0, 0) denoises every estimate with the
+        delay window.  Outputs per frame, each optional but not all: eq [n_dsym][Kd] complex64, its hard bits, csi [n_dsym][Kd]
+        float32, H_pat [n_pat][nfft] complex64, takes [n_pat] int32.  Returns n_dsym."""
+        out = self._track_out(d_eq, d_bits, d_csi, d_H_pat, d_takes)
+        return int(check(self.lib.ofdm_chan_track_frames(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
+                                                         ptr(d_tsr), int(mode), int(pre), int(post), int(bits_mode), C.byref(out),
+                                                         ptr(stream))))
+
+    def demod_frames_track(self, d_iq, n_frames, frame_stride, frame_len, mode=_lib.TRACK_LINEAR, d_eq=None, d_bits=None,
+                           bits_mode=BITS_NONE, d_csi=None, d_H_pat=None, d_takes=None, d_tsr=None, stream=None) -> int:
+        """ofdm_rx_demod_frames_track: the sync search of demod_frames, then chan_track_frames with the window of set_chan_window.
+        The averaging setting is not applied.  Returns n_dsym."""
+        out = self._track_out(d_eq, d_bits, d_csi, d_H_pat, d_takes)
+        return int(check(self.lib.ofdm_rx_demod_frames_track(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
+                                                             int(mode), int(bits_mode), ptr(d_tsr), C.byref(out), ptr(stream))))
+
     # ---- LTE tail-biting convolutional code: the decoder behind d_llr of demap_frames / demod_frames_soft / demod_frames_pilots ----
     def reserve_tbcc(self, n_blocks: int, K: int):
         """Prepares decoding of up to n_blocks code blocks of K bits per call (before a graph capture)."""
