@@ -370,6 +370,95 @@ int64_t ofdm_rx_demod_frames_mrc(ofdm_rx* h, const float* d_iq, int32_t n_branch
                                  int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
                                  const double* h_noise_var, const ofdm_mrc_out* out, double* d_sigma2_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ DFT-spread OFDM
+ * An extension the reference does not have: the LTE uplink waveform (SC-FDMA, TS 36.211 5.3.3).  The transmitter sends every row
+ * of M modulation symbols through an orthonormal M-point DFT before the resource grid (transform precoding); the receiver
+ * undoes it behind the one-tap equaliser (despreading).  M is any 2^a 3^b 5^c in 1 .. 4096 (137 sizes; ofdm_dft_size_ok), both
+ * directions carry 1/sqrt(M), twiddles come from a table built in fp64 and rounded once.  Behind the MMSE equaliser the despread
+ * symbol is biased and its noise is no longer the per-bin sigma^2/|H|^2: every symbol of a segment shares one gain beta and one
+ * post-despread variance nu.  ofdm_demap_csi_frames and ofdm_combine_csi_frames give WRONG weights if fed despread symbols; the
+ * LLR rule of this waveform is part of the stage below.  This text is the definition; tests/dft_spread_ref.py restates it in
+ * fp64 NumPy.
+ *
+ * Layout: segment s is `rows` rows of M complex64 at d_sym + s*seg_stride (complex items); entry k of every row of the segment
+ * has the channel power a = d_csi[s*csi_stride + k] (float32); rho (float32) is 1/SNR of the equaliser; sigma2 is a double per
+ * segment.
+ *  1. Entry mask.  Entry k is USABLE iff a is finite and > 0.  z'_k = z_k if the entry is usable and z_k.re, z_k.im are finite,
+ *     else z'_k = 0.
+ *  2. Inverse transform.  x_i = (1/sqrt(M)) sum_k z'_k e^(+2 pi j i k / M), in float32 and in the library's own operation order
+ *     (the bits are those of ofdm_dft_despread_frames with d_csi == NULL on the masked row).  A row whose z' are all 0+0j is an
+ *     erasure: sym = +0, llr = +0, bits those of a zero symbol.
+ *  3. Per-segment weights, in double: b_k = a/(a + rho) for usable entries and 0 for the others; beta = sum b_k / M;
+ *     nu = sum [(b_k - beta)^2 + sigma2 * a/(a + rho)^2] / M, the second term over usable entries only; w = beta^2 / nu.  The
+ *     sums run in a fixed order without atomics.  The segment is USABLE iff beta, nu and w are finite and > 0 and float(1/beta)
+ *     and float(w) are finite.  beta = float(beta) and weight = float(w), or +0 both where the segment is not usable.
+ *  4. Outputs.  u = x * float(1/beta) (float32, each product rounded); sym = u where the segment is usable, the row is no erasure
+ *     and u.re, u.im are finite, else +0+0j.  d per axis bit of the stored float32 sym exactly as steps 2-4 of the
+ *     channel-state-weighted LLR contract above (levels, labels, explicit minima, bit order).  llr = weight * d if the stored sym is not 0+0j and the product is finite
+ *     and not zero, else +0.  bits = ofdm_demap's hard rule on the stored sym.  No non-finite value leaves the call.
+ * Noise modes: OFDM_DESPREAD_NOISE_RHO sigma2 = rho, the equaliser's own assumption (nothing else needed);
+ * OFDM_DESPREAD_NOISE_GIVEN one host double noise_var, finite and > 0, read at call time (a captured graph keeps it);
+ * OFDM_DESPREAD_NOISE_SEG device doubles d_sigma2[n_seg] (a value that is not finite or <= 0 makes nu fail step 3's test or
+ * simply shifts it; the segment is then judged by step 3 alone).
+ * d_csi == NULL: the plain orthonormal inverse DFT -- every entry usable, beta = weight = 1, the noise mode ignored.
+ * sym agrees with the fp64 restatement to max|a-b|/max|b| < 1e-5; beta and weight within one float32 ulp (double sums rounded
+ * once); llr and bits are bit-exact functions of the device's own stored sym and weight.  The results depend on (rows, M) and
+ * the data alone: the same bits in any batch, at either alignment (8- or 16-byte row bases) and on every call. */
+typedef enum { OFDM_DESPREAD_NOISE_RHO = 0, OFDM_DESPREAD_NOISE_GIVEN = 1, OFDM_DESPREAD_NOISE_SEG = 2 } ofdm_despread_noise;
+typedef struct ofdm_despread_out {   /* DEVICE pointers; NULL = not wanted */
+    float*   sym;      /* [n_seg][rows*M] complex64, dense; may be d_sym itself where seg_stride == rows*M */
+    float*   llr;      /* [n_seg][rows*M*bps] float32, dense */
+    uint8_t* bits;     /* hard bits of sym: [n_seg][rows*M*bps] one per byte, or /8 bytes packed MSB-first */
+    float*   beta;     /* [n_seg] */
+    float*   weight;   /* [n_seg] */
+} ofdm_despread_out;
+/* Host calls, no GPU needed.  ofdm_dft_size_ok: 1 iff M = 2^a 3^b 5^c and 1 <= M <= 4096.  ofdm_dft_plan_info: the passes of
+ * the plan for M, how many of them are radix-8 (none: the plans use radix 3, 5, 4 and 2) and the rows a workgroup transforms at
+ * once; OFDM_ERR_INVALID for a size that is not ok.  Output pointers may be NULL. */
+int ofdm_dft_size_ok(int32_t M);
+int ofdm_dft_plan_info(int32_t M, int32_t* n_pass, int32_t* radix8, int32_t* rows_per_group);
+struct ofdm_tx;       /* the transmitter handle (typedef ofdm_tx below) */
+/* Transform precoder: n_rows contiguous rows of M complex64, out[r] = DFT_M(in[r]) / sqrt(M).  d_out == d_sym is allowed.
+ * Asynchronous on `stream`, one launch.  A plan for M that the handle does not hold yet is built first (see
+ * ofdm_tx_reserve_spread); inside a capture that is refused.  n_rows == 0: no-op. */
+int ofdm_tx_dft_spread(struct ofdm_tx* h, const float* d_sym, int64_t n_rows, int32_t M, float* d_out, void* stream);
+/* Builds and caches the plan for M (its twiddle table on the device; a handle keeps up to 8 plans, the least recently used one
+ * makes room) and sizes the workspace of ofdm_tx_modulate_frames_spread for n_rows data symbols.  Grows, never shrinks;
+ * synchronises the device.  Call it before capturing; inside a capture a call that needs a new plan or a larger workspace is
+ * refused before anything is enqueued. */
+int ofdm_tx_reserve_spread(struct ofdm_tx* h, int32_t M, int64_t n_rows);
+/* The stage calls ofdm_tx_map -> ofdm_tx_dft_spread (M = num_data_bins) -> ofdm_tx_grid -> ofdm_tx_ifft_cp(1, 1) -> ofdm_tx_mux over
+ * the handle's workspace: n_frames frames of n_sym symbols, the bits of frame f at d_bits + f * (bits or bytes per frame).
+ * Needs n_sym % (S + D) == 0 and frame_stride == n_sym*(nfft + cp), else OFDM_ERR_INVALID.  Pilots set by ofdm_tx_set_pilots pass
+ * through the grid untouched (they are not spread).  Returns the symbols written (n_frames * n_sym) or a negative error. */
+int64_t ofdm_tx_modulate_frames_spread(struct ofdm_tx* h, const uint8_t* d_bits, int32_t bits_mode, int64_t n_frames, int32_t n_sym,
+                                       float* d_iq, int64_t frame_stride, void* stream);
+/* The despreading stage on any device buffer (layout and steps above).  modulation 2, 4 or 6 (BPSK: OFDM_ERR_INVALID);
+ * bits_mode is read when out->bits is wanted.  Asynchronous on `stream`: two launches, no host synchronisation and no
+ * allocation once ofdm_rx_reserve_despread covers the call.  Zero counts or an M*rows*n_seg of 0 are a no-op.  Refusals are
+ * OFDM_ERR_INVALID with the reason in ofdm_last_error(), before anything is enqueued or any output touched: null handle, M not
+ * 2^a 3^b 5^c in 1 .. 4096, negative counts, seg_stride < rows*M, csi_stride < M, unknown noise_mode, OFDM_DESPREAD_NOISE_GIVEN
+ * with noise_var not finite or <= 0, OFDM_DESPREAD_NOISE_SEG without d_sigma2, rho negative or not finite, BPSK, bits wanted
+ * with OFDM_BITS_NONE or packed bits where M*bps % 8 != 0, `out` NULL or without any pointer, out->sym == d_sym with
+ * seg_stride != rows*M, index range exceeded (n_seg > 2^31, rows*M, n_seg*seg_stride or n_seg*csi_stride > 2^40, more than
+ * 2^31 - 1 workgroups).  Apart from out->sym == d_sym the buffers must not overlap. */
+int ofdm_dft_despread_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int32_t M, int64_t seg_stride,
+                             const float* d_csi, int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode,
+                             double noise_var, const double* d_sigma2, int32_t bits_mode, const ofdm_despread_out* out,
+                             void* stream);
+/* Plan cache and capture rule as ofdm_tx_reserve_spread; sizes the per-segment table for n_seg segments and the |H|^2 rows of
+ * ofdm_rx_demod_frames_despread (n_seg frames). */
+int ofdm_rx_reserve_despread(ofdm_rx* h, int32_t M, int64_t n_seg);
+/* ofdm_rx_demod_frames (d_eq required, no hard bits of the equalised rows; same d_eq / d_tsr bits and return value n_dsym), then
+ * ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL) into the workspace, then the stage over d_eq with one segment per frame: rows = n_dsym,
+ * M = num_data_bins, rho = 1/snr_data of the handle's equaliser, modulation = cfg.modulation.  It runs the handle's ordinary
+ * sync and demod and so follows ofdm_rx_set_chan_window and ofdm_rx_set_chan_average like every ofdm_rx_demod_frames_* call.
+ * Signals with pilots: chain ofdm_rx_demod_frames_pilots -> ofdm_rx_csi_frames(OFDM_CSI_ROWS_DATA) -> ofdm_dft_despread_frames over
+ * its out->data (rows = n_dsym, M = Kd'). */
+int64_t ofdm_rx_demod_frames_despread(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                      float* d_eq, int32_t* d_tsr, int32_t noise_mode, double noise_var, const double* d_sigma2,
+                                      int32_t bits_mode, const ofdm_despread_out* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ delay-window channel-estimate denoising
  * An extension the reference does not have.  The batch receiver's channel estimate is the least-squares (LS) estimate of ONE
  * Zadoff-Chu preamble symbol: as noisy as one received symbol.  A channel is shorter than the cyclic prefix, so nearly all of that

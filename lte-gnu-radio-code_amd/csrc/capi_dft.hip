@@ -1,0 +1,292 @@
+// capi_dft.hip -- DFT-spread OFDM on both handles: the plan cache, the transform precoder and the composite transmitter, the
+// despreading stage and the call that chains it behind ofdm_rx_demod_frames (definition: include/ofdm_mi355x.h, "DFT-spread
+// OFDM").
+#include "capi_internal.hpp"
+
+void dft_plans_free(DftPlanCache& c) {
+    for (int i = 0; i < c.n; ++i) free_dev(&c.d_tw[i]);
+    c.n = 0;
+}
+
+namespace {
+
+int dft_plan_find(DftPlanCache& c, int M) {
+    for (int i = 0; i < c.n; ++i)
+        if (c.pl[i].M == M) {
+            c.used[i] = ++c.tick;
+            return i;
+        }
+    return -1;
+}
+// builds the plan for M (a size that is ok) into the cache; the least recently used one makes room
+template <class H>
+int dft_plan_build(H* h, int M, int* slot) {
+    DftPlanCache& c = h->dft;
+    DftPlan pl;
+    dft_make_plan(M, pl);
+    std::vector<cf> tw(size_t(M), cf{1.f, 0.f});
+    for (int j = 0; j < M; ++j) {
+        const double ang = -2.0 * M_PI * double(j) / double(M);
+        tw[size_t(j)] = cf{float(std::cos(ang)), float(std::sin(ang))};
+    }
+    HIP_TRY(dft_spread_prepare());
+    if (c.n == DftPlanCache::SLOTS) {
+        int v = 0;
+        for (int i = 1; i < c.n; ++i)
+            if (c.used[i] < c.used[v]) v = i;
+        const int drained = drain(h);                       // work queued on a caller's stream may still read the table
+        if (drained != OFDM_OK) return drained;
+        free_dev(&c.d_tw[v]);
+        const int last = c.n - 1;
+        c.pl[v] = c.pl[last];
+        c.d_tw[v] = c.d_tw[last];
+        c.used[v] = c.used[last];
+        c.d_tw[last] = nullptr;
+        c.n = last;
+    }
+    const int rc = upload(&c.d_tw[c.n], tw);
+    if (rc != OFDM_OK) {
+        free_dev(&c.d_tw[c.n]);
+        return rc;
+    }
+    c.pl[c.n] = pl;
+    c.used[c.n] = ++c.tick;
+    *slot = c.n++;
+    return OFDM_OK;
+}
+const char* dft_bad_size(int32_t M) { return dft_size_ok(M) ? "" : "M must be 2^a 3^b 5^c in 1 .. 4096"; }
+bool dft_rows_in_range(const DftPlan& pl, int64_t rows, int64_t n_seg) {
+    const int64_t groups = (rows + pl.rows_per_group - 1) / pl.rows_per_group;
+    return n_seg <= 0 || groups <= DFT_MAX_GROUPS / n_seg;
+}
+
+// ---- transmitter
+int tx_spread_ensure(ofdm_tx* h, int32_t M, int64_t ws_rows, hipStream_t s, const char* who, int* slot) {
+    *slot = dft_plan_find(h->dft, M);
+    if (*slot >= 0 && ws_rows <= h->cap_sp_rows) return OFDM_OK;
+    int rc = refuse_growth_in_capture(s, who, "ofdm_tx_reserve_spread");
+    if (rc == OFDM_OK) rc = ofdm_tx_reserve_spread(h, M, ws_rows);
+    if (rc == OFDM_OK) *slot = dft_plan_find(h->dft, M);
+    return rc;
+}
+
+// ---- receiver
+bool despread_wanted(const ofdm_despread_out* o) { return o && (o->sym || o->llr || o->bits || o->beta || o->weight); }
+// what the arguments alone decide (no read of the handle, no device access); "" = fine
+const char* despread_bad_args(const float* d_sym, int64_t n_seg, int64_t rows, int32_t M, int64_t seg_stride, bool has_csi,
+                              int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode, double noise_var,
+                              const double* d_sigma2, int32_t bits_mode, const ofdm_despread_out* out) {
+    if (*dft_bad_size(M)) return dft_bad_size(M);
+    if (n_seg < 0 || rows < 0) return "negative count";
+    if (rows > SOFT_MAX_LEN / M) return "index range exceeded (rows * M)";
+    if (seg_stride < rows * M) return "seg_stride < rows * M";
+    if (!soft_mod_ok(modulation)) return "modulation must be 2, 4 or 6 bits per symbol (no BPSK soft metrics)";
+    if (has_csi) {
+        if (csi_stride < M) return "csi_stride < M";
+        if (noise_mode != OFDM_DESPREAD_NOISE_RHO && noise_mode != OFDM_DESPREAD_NOISE_GIVEN && noise_mode != OFDM_DESPREAD_NOISE_SEG)
+            return "noise_mode must be OFDM_DESPREAD_NOISE_RHO, OFDM_DESPREAD_NOISE_GIVEN or OFDM_DESPREAD_NOISE_SEG";
+        if (noise_mode == OFDM_DESPREAD_NOISE_GIVEN && !(std::isfinite(noise_var) && noise_var > 0.0))
+            return "OFDM_DESPREAD_NOISE_GIVEN needs a finite noise_var > 0";
+        if (noise_mode == OFDM_DESPREAD_NOISE_SEG && !d_sigma2) return "OFDM_DESPREAD_NOISE_SEG needs d_sigma2";
+        if (!(std::isfinite(rho) && rho >= 0.f)) return "rho must be finite and >= 0";
+    }
+    if (!despread_wanted(out)) return "out is NULL or holds no pointer";
+    if (out->bits) {
+        if (!bits_mode_ok(bits_mode)) return "bits wanted: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        if (bits_mode == OFDM_BITS_PACKED && (int64_t(M) * modulation) % 8 != 0) return "packed bits need M * bits per symbol % 8 == 0";
+    }
+    if (out->sym && out->sym == d_sym && seg_stride != rows * M) return "out->sym == d_sym needs seg_stride == rows * M";
+    if (n_seg > SOFT_MAX_N || (n_seg > 0 && (seg_stride > SOFT_MAX_LEN / n_seg || (has_csi && csi_stride > SOFT_MAX_LEN / n_seg))))
+        return "index range exceeded (batch beyond the kernels' index range)";
+    DftPlan pl;
+    dft_make_plan(M, pl);
+    if (!dft_rows_in_range(pl, rows, n_seg)) return "index range exceeded (more than 2^31 - 1 workgroups)";
+    return "";
+}
+// the plan for M and the tables of n_seg segments (frames: also their |H|^2 rows), or a refusal inside a capture
+int despread_ensure(ofdm_rx* h, int32_t M, int64_t n_seg, hipStream_t s, const char* who, int* slot) {
+    *slot = dft_plan_find(h->dft, M);
+    if (*slot >= 0 && n_seg <= h->cap_ds_seg) return OFDM_OK;
+    int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_despread");
+    if (rc == OFDM_OK) rc = ofdm_rx_reserve_despread(h, M, n_seg);
+    if (rc == OFDM_OK) *slot = dft_plan_find(h->dft, M);
+    return rc;
+}
+int despread_launch(ofdm_rx* h, int slot, const float* d_sym, int64_t n_seg, int64_t rows, int64_t seg_stride, const float* d_csi,
+                    int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode, double noise_var, const double* d_sigma2,
+                    int32_t bits_mode, const ofdm_despread_out* out, hipStream_t s) {
+    DespreadArgs a{};
+    a.pl = h->dft.pl[slot];
+    a.tw = h->dft.d_tw[slot];
+    a.sym = reinterpret_cast<const cf*>(d_sym);
+    a.n_seg = n_seg;
+    a.rows = rows;
+    a.seg_stride = seg_stride;
+    a.groups_per_seg = (rows + a.pl.rows_per_group - 1) / a.pl.rows_per_group;
+    a.csi = d_csi;
+    a.csi_stride = csi_stride;
+    a.rho = rho;
+    a.noise_mode = noise_mode;
+    a.noise_var = noise_var;
+    a.sigma2 = d_sigma2;
+    a.mod = modulation;
+    a.bits_mode = bits_mode;
+    a.osym = reinterpret_cast<cf*>(out->sym);
+    a.llr = out->llr;
+    a.bits = out->bits;
+    a.beta = out->beta;
+    a.weight = out->weight;
+    a.tab = h->ds_tab;
+    HIP_TRY(launch_despread(a, s));
+    return OFDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofdm_dft_size_ok(int32_t M) { return dft_size_ok(M) ? 1 : 0; }
+
+int ofdm_dft_plan_info(int32_t M, int32_t* n_pass, int32_t* radix8, int32_t* rows_per_group) {
+    DftPlan pl;
+    if (!dft_make_plan(M, pl)) return fail(OFDM_ERR_INVALID, "ofdm_dft_plan_info: %s", dft_bad_size(M));
+    if (n_pass) *n_pass = pl.n_pass;
+    if (radix8) *radix8 = 0;
+    if (rows_per_group) *rows_per_group = pl.rows_per_group;
+    return OFDM_OK;
+}
+
+int ofdm_tx_reserve_spread(ofdm_tx* h, int32_t M, int64_t n_rows) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_spread: null handle");
+    if (*dft_bad_size(M)) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_spread: %s", dft_bad_size(M));
+    if (n_rows < 0) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_spread: negative count");
+    if (n_rows > INT32_MAX) return fail(OFDM_ERR_INVALID, "ofdm_tx_reserve_spread: batch too large");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    int slot = dft_plan_find(h->dft, M);
+    if (slot < 0) {
+        const int rc = dft_plan_build(h, M, &slot);
+        if (rc != OFDM_OK) return rc;
+    }
+    if (n_rows <= h->cap_sp_rows) return OFDM_OK;
+    const TxDev& d = h->dev;
+    return regrow(h, {{&h->cap_sp_rows, n_rows}}, ws_buf(&h->sp_sym, size_t(n_rows) * d.Kd), ws_buf(&h->sp_grid, size_t(n_rows) * d.nfft),
+                  ws_buf(&h->sp_time, size_t(n_rows) * d.L));
+}
+
+int ofdm_tx_dft_spread(ofdm_tx* h, const float* d_sym, int64_t n_rows, int32_t M, float* d_out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_tx_dft_spread: null handle");
+    if (*dft_bad_size(M)) return fail(OFDM_ERR_INVALID, "ofdm_tx_dft_spread: %s", dft_bad_size(M));
+    if (n_rows < 0) return fail(OFDM_ERR_INVALID, "ofdm_tx_dft_spread: negative count");
+    DftPlan pl;
+    dft_make_plan(M, pl);
+    if (n_rows > SOFT_MAX_LEN / M || !dft_rows_in_range(pl, n_rows, 1)) return fail(OFDM_ERR_INVALID, "ofdm_tx_dft_spread: index range exceeded");
+    if (n_rows == 0) return OFDM_OK;
+    if (!d_sym || !d_out) return fail(OFDM_ERR_INVALID, "ofdm_tx_dft_spread: null d_sym or d_out");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = pick_stream(h, stream);
+    int slot = -1;
+    const int rc = tx_spread_ensure(h, M, 0, s, "ofdm_tx_dft_spread", &slot);
+    if (rc != OFDM_OK) return rc;
+    HIP_TRY(launch_dft_rows(h->dft.pl[slot], h->dft.d_tw[slot], reinterpret_cast<const cf*>(d_sym), reinterpret_cast<cf*>(d_out), n_rows,
+                            0, s));
+    return OFDM_OK;
+}
+
+int64_t ofdm_tx_modulate_frames_spread(ofdm_tx* h, const uint8_t* d_bits, int32_t bits_mode, int64_t n_frames, int32_t n_sym,
+                                       float* d_iq, int64_t frame_stride, void* stream) {
+    const char* who = "ofdm_tx_modulate_frames_spread";
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    if (n_frames < 0 || n_sym < 0) return fail(OFDM_ERR_INVALID, "%s: negative count", who);
+    if (!bits_mode_ok(bits_mode)) return fail(OFDM_ERR_INVALID, "%s: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED", who);
+    const TxDev& d = h->dev;
+    const int SD = d.S + d.D;
+    if (n_sym % SD != 0) return fail(OFDM_ERR_INVALID, "%s: n_sym must be a multiple of S + D = %d", who, SD);
+    if (frame_stride != int64_t(n_sym) * d.L) return fail(OFDM_ERR_INVALID, "%s: frame_stride must equal n_sym*(nfft+cp)", who);
+    if (*dft_bad_size(d.Kd)) return fail(OFDM_ERR_INVALID, "%s: num_data_bins=%d: %s", who, d.Kd, dft_bad_size(d.Kd));
+    if (n_frames * int64_t(n_sym) > INT32_MAX) return fail(OFDM_ERR_INVALID, "%s: batch too large", who);
+    const int64_t data_per_frame = int64_t(n_sym / SD) * d.D, rows = n_frames * data_per_frame;
+    const int64_t bits_per_frame = data_per_frame * d.Kd * d.bps;
+    if (bits_mode == OFDM_BITS_PACKED && (bits_per_frame & 7)) return fail(OFDM_ERR_INVALID, "%s: packed bits need a whole number of bytes per frame", who);
+    if (rows == 0) return 0;
+    if (!d_bits || !d_iq) return fail(OFDM_ERR_INVALID, "%s: null d_bits or d_iq", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    int slot = -1;
+    int rc = tx_spread_ensure(h, d.Kd, rows, pick_stream(h, stream), who, &slot);
+    if (rc != OFDM_OK) return rc;
+    float* sym = reinterpret_cast<float*>(h->sp_sym);
+    float* grid = reinterpret_cast<float*>(h->sp_grid);
+    float* time = reinterpret_cast<float*>(h->sp_time);
+    rc = ofdm_tx_map(h, d_bits, bits_mode, rows * d.Kd, sym, stream);
+    if (rc == OFDM_OK) rc = ofdm_tx_dft_spread(h, sym, rows, d.Kd, sym, stream);
+    if (rc == OFDM_OK) rc = ofdm_tx_grid(h, sym, rows, grid, stream);
+    if (rc == OFDM_OK) rc = ofdm_tx_ifft_cp(h, grid, rows, 1, 1, time, stream);
+    if (rc != OFDM_OK) return rc;
+    return ofdm_tx_mux(h, time, rows, d_iq, stream);
+}
+
+int ofdm_rx_reserve_despread(ofdm_rx* h, int32_t M, int64_t n_seg) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_despread: null handle");
+    if (*dft_bad_size(M)) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_despread: %s", dft_bad_size(M));
+    if (n_seg < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_despread: negative count");
+    if (n_seg > SOFT_MAX_N) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_despread: batch too large");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    int slot = dft_plan_find(h->dft, M);
+    if (slot < 0) {
+        const int rc = dft_plan_build(h, M, &slot);
+        if (rc != OFDM_OK) return rc;
+    }
+    if (n_seg <= h->cap_ds_seg) return OFDM_OK;
+    return regrow(h, {{&h->cap_ds_seg, n_seg}}, ws_buf(&h->ds_tab, size_t(n_seg)), ws_buf(&h->ds_a, size_t(n_seg) * h->dev.Kd));
+}
+
+int ofdm_dft_despread_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int32_t M, int64_t seg_stride,
+                             const float* d_csi, int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode,
+                             double noise_var, const double* d_sigma2, int32_t bits_mode, const ofdm_despread_out* out, void* stream) {
+    if (!h) return fail(OFDM_ERR_INVALID, "ofdm_dft_despread_frames: null handle");
+    const char* bad = despread_bad_args(d_sym, n_seg, rows, M, seg_stride, d_csi != nullptr, csi_stride, rho, modulation, noise_mode,
+                                        noise_var, d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "ofdm_dft_despread_frames: %s", bad);
+    if (n_seg == 0 || rows == 0) return OFDM_OK;
+    if (!d_sym) return fail(OFDM_ERR_INVALID, "ofdm_dft_despread_frames: null d_sym");
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = pick_stream(h, stream);
+    int slot = -1;
+    const int rc = despread_ensure(h, M, n_seg, s, "ofdm_dft_despread_frames", &slot);
+    if (rc != OFDM_OK) return rc;
+    return despread_launch(h, slot, d_sym, n_seg, rows, seg_stride, d_csi, csi_stride, rho, modulation, noise_mode, noise_var, d_sigma2,
+                           bits_mode, out, s);
+}
+
+int64_t ofdm_rx_demod_frames_despread(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                      float* d_eq, int32_t* d_tsr, int32_t noise_mode, double noise_var, const double* d_sigma2,
+                                      int32_t bits_mode, const ofdm_despread_out* out, void* stream) {
+    const char* who = "ofdm_rx_demod_frames_despread";
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, who);
+    if (open != OFDM_OK) return open;
+    if (!d_eq) return fail(OFDM_ERR_INVALID, "%s: the despreading stage needs d_eq (it reads it)", who);
+    const RxDev& d = h->dev;
+    const int mod = h->cfg.modulation;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
+    // the checks of the stages, made here first so that a bad call enqueues nothing
+    const char* bad = demod_bad_args(d, n_frames, n_dsym, nullptr, OFDM_BITS_NONE);
+    if (!*bad)
+        bad = despread_bad_args(d_eq, n_frames, n_dsym, d.Kd, n_dsym * d.Kd, true, d.Kd, d.inv_snr_data, mod, noise_mode, noise_var,
+                                d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    hipStream_t s = pick_stream(h, stream);
+    const bool run = n_frames > 0 && n_dsym > 0;
+    int slot = -1;
+    if (run) {                                              // grow first: nothing is enqueued unless the whole call can run
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        const int rc = despread_ensure(h, d.Kd, n_frames, s, who, &slot);
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t r = ofdm_rx_demod_frames(h, d_iq, n_frames, frame_stride, frame_len, d_eq, nullptr, OFDM_BITS_NONE, d_tsr, stream);
+    if (r < 0 || !run) return r;
+    HIP_TRY(launch_csi_frames(h->f_H, d.nfft, d.Kd, nullptr, d.Kd, n_frames, h->ds_a, d.Kd, s));
+    const int rc = despread_launch(h, slot, d_eq, n_frames, n_dsym, n_dsym * d.Kd, h->ds_a, d.Kd, d.inv_snr_data, mod, noise_mode, noise_var,
+                                   d_sigma2, bits_mode, out, s);
+    return rc != OFDM_OK ? rc : r;
+}
+
+}  // extern "C"

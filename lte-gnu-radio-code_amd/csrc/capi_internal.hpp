@@ -44,6 +44,16 @@ int rx_sync_leg(ofdm_rx* h, const cf* iq, int64_t n_frames, int64_t frame_stride
         if (e_ != hipSuccess) return fail(OFDM_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
+// DFT-spread OFDM: the plans a handle holds (capi_dft.hip).  A plan is its DftPlan and the twiddle table on the device.
+struct DftPlanCache {
+    static constexpr int SLOTS = 8;
+    DftPlan pl[SLOTS] = {};
+    cf* d_tw[SLOTS] = {};
+    uint64_t used[SLOTS] = {};           // tick of the last use: the smallest one makes room
+    uint64_t tick = 0;
+    int n = 0;
+};
+
 struct ofdm_rx {
     ofdm_rx_cfg cfg{};
     hipStream_t stream = nullptr;
@@ -135,6 +145,11 @@ struct ofdm_rx {
     int64_t cap_mrc_tab = 0;
     double* m_sigma2 = nullptr;          // [n_branch*n_seg] estimated variances of ofdm_rx_demod_frames_mrc
     int64_t cap_mrc_units = 0;
+    // ---- DFT-spread OFDM (ofdm_rx_reserve_despread)
+    DftPlanCache dft{};
+    float4* ds_tab = nullptr;            // [n_seg] {float(1/beta), weight, beta, usable} (DespreadArgs)
+    float* ds_a = nullptr;               // [n_seg][Kd] |H|^2 rows of ofdm_rx_demod_frames_despread
+    int64_t cap_ds_seg = 0;
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;
@@ -231,7 +246,18 @@ struct ofdm_tx {
     // ---- transport-block layer (ofdm_tx_reserve_tb): the packed code blocks per group, then the groups' encoder outputs
     uint8_t* tb_ws = nullptr;
     int64_t cap_tb = 0;                  // bytes
+    // ---- DFT-spread OFDM (ofdm_tx_reserve_spread): the plans, and the rows between the stages of ofdm_tx_modulate_frames_spread
+    DftPlanCache dft{};
+    cf* sp_sym = nullptr;                // [rows][Kd]
+    cf* sp_grid = nullptr;               // [rows][nfft]
+    cf* sp_time = nullptr;               // [rows][L]
+    int64_t cap_sp_rows = 0;
 };
+
+// capi_dft.hip: frees the tables of a handle's plans (the destroys)
+#pragma GCC visibility push(hidden)
+void dft_plans_free(DftPlanCache& c);
+#pragma GCC visibility pop
 
 namespace {
 

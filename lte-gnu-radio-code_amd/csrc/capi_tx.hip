@@ -8,7 +8,8 @@ int ofdm_tx_destroy(ofdm_tx* h) {
     if (!h) return OFDM_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_dev(&h->d_tw, &h->d_zc, &h->d_sync_time, &h->d_pilots, &h->tb_ws);
+    free_dev(&h->d_tw, &h->d_zc, &h->d_sync_time, &h->d_pilots, &h->tb_ws, &h->sp_sym, &h->sp_grid, &h->sp_time);
+    dft_plans_free(h->dft);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return OFDM_OK;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <vector>
 #include "ofdm_device.hpp"
+#include "dft_mixed.hpp"
 
 namespace ofdm {
 
@@ -191,6 +192,37 @@ struct MrcArgs {
     float2* tab;             // [n_branch*n_seg][row_len] workspace
 };
 hipError_t launch_combine_mrc(const MrcArgs& a, hipStream_t s);
+
+// ---- DFT-spread OFDM (dft_spread.hip; contract: include/ofdm_mi355x.h, "DFT-spread OFDM").  A plan (DftPlan,
+// dft_mixed.hpp) and its table tw[M] = e^(-2 pi i j / M) serve both directions.  One workgroup per group of
+// pl.rows_per_group consecutive rows: the grid is not capped, the callers bound the number of groups by DFT_MAX_GROUPS.
+constexpr int64_t DFT_MAX_GROUPS = (int64_t(1) << 31) - 1;
+hipError_t launch_dft_rows(const DftPlan& pl, const cf* tw, const cf* in, cf* out, int64_t n_rows, int inverse, hipStream_t s);
+// despreading stage (ofdm_dft_despread_frames): segment s = rows rows of pl.M symbols at sym + s*seg_stride; entry k of every row
+// of segment s has the channel power csi[s*csi_stride + k]
+struct DespreadArgs {
+    DftPlan pl;
+    const cf* tw;
+    const cf* sym;
+    int64_t n_seg, rows, seg_stride;      // complex items
+    int64_t groups_per_seg;  // ceil(rows / pl.rows_per_group)
+    const float* csi;        // [n_seg][csi_stride] |H|^2 per entry, or null (plain inverse transform, beta = weight = 1)
+    int64_t csi_stride;
+    float rho;               // 1 / SNR of the equaliser
+    int noise_mode;          // ofdm_despread_noise
+    double noise_var;        // GIVEN: sigma^2 of every segment
+    const double* sigma2;    // SEG: [n_seg]
+    int mod;                 // 2, 4, 6 (read when llr or bits is wanted)
+    int bits_mode;           // ofdm_bits_mode
+    cf* osym;                // [n_seg][rows*M], or null; may be sym where seg_stride == rows*M
+    float* llr;              // [n_seg][rows*M*mod], or null
+    uint8_t* bits;           // hard bits of osym, or null
+    float* beta;             // [n_seg], or null
+    float* weight;           // [n_seg], or null
+    float4* tab;             // [n_seg] workspace {float(1/beta), weight, beta, usable}
+};
+hipError_t launch_despread(const DespreadArgs& a, hipStream_t s);
+hipError_t dft_spread_prepare();         // loads the kernels (before a stream capture)
 
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of

@@ -29,6 +29,7 @@ CSI_ROWS_ALL, CSI_ROWS_DATA = 0, 1
 MRC_NOISE_GIVEN, MRC_NOISE_SEG, MRC_NOISE_EST = 0, 1, 2
 MRC_MAX_BRANCHES = 8
 TRACK_HOLD, TRACK_LINEAR = 0, 1
+DESPREAD_NOISE_RHO, DESPREAD_NOISE_GIVEN, DESPREAD_NOISE_SEG = 0, 1, 2
 MODULATION_BITS = {"BPSK": 1, "QPSK": 2, "16QAM": 4, "64QAM": 6}
 
 
@@ -91,6 +92,11 @@ class PilotOut(C.Structure):
 class CsiOut(C.Structure):
     """ofdm_csi_out: device pointers of the channel-state-weighted LLR stage (None = not wanted)."""
     _fields_ = [("llr", C.c_void_p), ("sigma2", C.c_void_p), ("n_used", C.c_void_p)]
+
+
+class DespreadOut(C.Structure):
+    """ofdm_despread_out: device pointers of the DFT-spread OFDM despreading stage (None = not wanted)."""
+    _fields_ = [("sym", C.c_void_p), ("llr", C.c_void_p), ("bits", C.c_void_p), ("beta", C.c_void_p), ("weight", C.c_void_p)]
 
 
 class MrcOut(C.Structure):
@@ -198,6 +204,18 @@ PROTOTYPES = {
                                         C.c_float, C.c_int32, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
     "ofdm_rx_demod_frames_csi": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                              C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.POINTER(CsiOut), C.c_void_p]),
+    "ofdm_dft_size_ok": (C.c_int, [C.c_int32]),
+    "ofdm_dft_plan_info": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ofdm_tx_dft_spread": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ofdm_tx_reserve_spread": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    "ofdm_tx_modulate_frames_spread": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                   C.c_void_p]),
+    "ofdm_dft_despread_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_float, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int32,
+                                           C.POINTER(DespreadOut), C.c_void_p]),
+    "ofdm_rx_reserve_despread": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    "ofdm_rx_demod_frames_despread": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_int32, C.c_double, C.c_void_p, C.c_int32, C.POINTER(DespreadOut), C.c_void_p]),
     "ofdm_chan_window_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     "ofdm_rx_set_chan_window": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),

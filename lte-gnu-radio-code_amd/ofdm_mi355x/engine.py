@@ -149,6 +149,18 @@ def turbo_qpp_check(K: int, f1: int, f2: int) -> bool:
     return _lib.load().ofdm_turbo_qpp_check(int(K), int(f1), int(f2)) == 0
 
 
+def dft_size_ok(M: int) -> bool:
+    """ofdm_dft_size_ok: True iff M = 2^a 3^b 5^c and 1 <= M <= 4096, the sizes of the DFT-spread OFDM transforms."""
+    return -2 ** 31 <= int(M) < 2 ** 31 and _lib.load().ofdm_dft_size_ok(int(M)) == 1
+
+
+def dft_plan_info(M: int) -> tuple:
+    """ofdm_dft_plan_info: (passes, radix-8 passes among them, rows a workgroup transforms at once) of the plan for M."""
+    n_pass, radix8, rpg = C.c_int32(), C.c_int32(), C.c_int32()
+    check(_lib.load().ofdm_dft_plan_info(int(M), C.byref(n_pass), C.byref(radix8), C.byref(rpg)))
+    return int(n_pass.value), int(radix8.value), int(rpg.value)
+
+
 def crc_bits(kind: int) -> int:
     """ofdm_crc_bits: the parity bits L of a CRC kind (CRC24A, CRC24B: 24, CRC16: 16, CRC8: 8)."""
     return int(check(_lib.load().ofdm_crc_bits(int(kind))))
@@ -376,6 +388,37 @@ class RxEngine(_Handle):
         return int(check(self.lib.ofdm_rx_demod_frames_csi(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
                                                            ptr(d_eq), ptr(d_bits), int(bits_mode), ptr(d_tsr), int(noise_mode),
                                                            float(noise_var), C.byref(out), ptr(stream))))
+
+    # ---- DFT-spread OFDM (SC-FDMA): despreading behind the equaliser (include/ofdm_mi355x.h, "DFT-spread OFDM") ----------------
+    @staticmethod
+    def _despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight):
+        return _lib.DespreadOut(_addr(d_sym_out), _addr(d_llr), _addr(d_bits), _addr(d_beta), _addr(d_weight))
+
+    def reserve_despread(self, M: int, n_seg: int = 0):
+        """ofdm_rx_reserve_despread: the plan for M and the tables of n_seg segments (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_despread(self._h, int(M), int(n_seg)))
+
+    def dft_despread_frames(self, d_sym, n_seg, rows, M, seg_stride, d_csi, csi_stride, rho, modulation, d_sym_out=None, d_llr=None,
+                            d_bits=None, bits_mode=BITS_NONE, d_beta=None, d_weight=None, noise_mode=_lib.DESPREAD_NOISE_RHO,
+                            noise_var=0.0, d_sigma2=None, stream=None):
+        """ofdm_dft_despread_frames: segment s = `rows` rows of M equalised complex64 symbols at d_sym + s*seg_stride, entry k of
+        every row with the channel power d_csi[s*csi_stride + k] (d_csi None: the plain inverse transform).  Outputs sym
+        [n_seg][rows*M] complex64 (may be d_sym), llr [n_seg][rows*M*bps] (positive favours bit 0), hard bits, beta and weight
+        [n_seg] float32."""
+        out = self._despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight)
+        check(self.lib.ofdm_dft_despread_frames(self._h, ptr(d_sym), int(n_seg), int(rows), int(M), int(seg_stride), ptr(d_csi),
+                                                int(csi_stride), float(rho), _mod_bits(modulation), int(noise_mode), float(noise_var),
+                                                ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream)))
+
+    def demod_frames_despread(self, d_iq, n_frames, frame_stride, frame_len, d_eq, d_sym_out=None, d_llr=None, d_bits=None,
+                              bits_mode=BITS_NONE, d_beta=None, d_weight=None, noise_mode=_lib.DESPREAD_NOISE_RHO, noise_var=0.0,
+                              d_sigma2=None, d_tsr=None, stream=None) -> int:
+        """demod_frames, then csi_frames(CSI_ROWS_ALL) into the workspace and dft_despread_frames over d_eq with one segment per
+        frame (n_dsym rows of M = Kd symbols, the handle's rho and modulation).  Returns n_dsym."""
+        out = self._despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight)
+        return int(check(self.lib.ofdm_rx_demod_frames_despread(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
+                                                                ptr(d_eq), ptr(d_tsr), int(noise_mode), float(noise_var),
+                                                                ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream))))
 
     # ---- receive-diversity combining: B branches added with maximum-ratio weights, LLRs of the sum (include/ofdm_mi355x.h) ------
     @staticmethod
@@ -854,6 +897,24 @@ class TxEngine(_Handle):
 
     def mux(self, d_data, n_data_sym, d_out, stream=None) -> int:
         return int(check(self.lib.ofdm_tx_mux(self._h, ptr(d_data), int(n_data_sym), ptr(d_out), ptr(stream))))
+
+    # ---- DFT-spread OFDM (SC-FDMA): transform precoding (include/ofdm_mi355x.h, "DFT-spread OFDM")
+    def reserve_spread(self, M: int, n_rows: int = 0):
+        """ofdm_tx_reserve_spread: the plan for M and the workspace of modulate_frames_spread for n_rows data symbols (before a
+        graph capture)."""
+        check(self.lib.ofdm_tx_reserve_spread(self._h, int(M), int(n_rows)))
+
+    def dft_spread(self, d_sym, n_rows, M, d_out, stream=None):
+        """ofdm_tx_dft_spread: n_rows contiguous rows of M complex64 -> their orthonormal M-point DFTs; d_out may be d_sym."""
+        check(self.lib.ofdm_tx_dft_spread(self._h, ptr(d_sym), int(n_rows), int(M), ptr(d_out), ptr(stream)))
+
+    def modulate_frames_spread(self, d_bits, n_frames, n_sym, d_iq, frame_stride=None, bits_mode=BITS_UNPACKED, stream=None) -> int:
+        """ofdm_tx_modulate_frames_spread: map -> dft_spread (M = num_data_bins) -> grid -> ifft_cp -> mux over the handle's
+        workspace.  n_sym must be a multiple of S + D and frame_stride n_sym*(nfft+cp).  Returns the symbols written."""
+        if frame_stride is None:
+            frame_stride = int(n_sym) * (self.cfg.nfft + self.cfg.cp_len)
+        return int(check(self.lib.ofdm_tx_modulate_frames_spread(self._h, ptr(d_bits), int(bits_mode), int(n_frames), int(n_sym),
+                                                                 ptr(d_iq), int(frame_stride), ptr(stream))))
 
     def sync_symbol(self) -> np.ndarray:
         c = self.cfg
