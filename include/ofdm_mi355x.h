@@ -459,6 +459,86 @@ int64_t ofdm_rx_demod_frames_despread(ofdm_rx* h, const float* d_iq, int64_t n_f
                                       float* d_eq, int32_t* d_tsr, int32_t noise_mode, double noise_var, const double* d_sigma2,
                                       int32_t bits_mode, const ofdm_despread_out* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ receive diversity for DFT-spread OFDM
+ * An extension the reference does not have: B receive branches (antennas) of a DFT-spread signal.  The branches are combined per
+ * bin in the frequency domain FIRST and the combined row is despread afterwards, so that the gain and the noise behind the
+ * inverse transform come from the COMBINED channel.  (ofdm_combine_csi_frames followed by ofdm_dft_despread_frames, or despreading
+ * per branch and adding, give wrong weights.)  This text is the definition; tests/mrc_despread_ref.py restates it in NumPy.
+ *
+ * Layout as ofdm_combine_csi_frames, branch-major: branch b of segment s is the unit g = b*n_seg + s: `rows` rows of M complex64
+ * equalised symbols at d_sym + g*seg_stride (complex items), channel powers a = |H|^2 at d_csi + g*csi_stride (float32), one
+ * noise variance sigma2[g] (double) per unit, rho the equaliser's float32 term.  M is any size ofdm_dft_size_ok accepts, B is
+ * 1 .. OFDM_MRC_MAX_BRANCHES.
+ *  1.-3. Exactly steps 1-3 of the receive-diversity contract above with row_len = M: c = (a + rho)/w_den and t = a/w_den per (unit,
+ *     entry) with the USABLE rule for entries, p = z*c with the TAKES PART rule for a branch of a symbol, N = sum p and A = sum t
+ *     from +0 in branch order.  All float32, every operation rounded on its own (no fused multiply-add).
+ *  4. MMSE combining per bin, float32: den = A + 1.0f, v = (N.re/den, N.im/den).  The symbol is COMBINED iff at least one branch
+ *     took part, A is finite and > 0, and v is finite; otherwise v = 0+0j and A counts as 0 in step 6.  With unit-power symbols
+ *     v_k = b_k X_k + noise with b_k = A/(A + 1) and noise variance b_k (1 - b_k).  The "1" is the symbols' power in units of the
+ *     noise variances: unlike ofdm_combine_csi_frames, whose u = N/A does not see a common factor of the sigma2, the ABSOLUTE
+ *     level of the variances matters here -- variances too small by a factor f act as an equaliser tuned to an SNR f too high.
+ *  5. Inverse transform of the row of v: x_i = (1/sqrt(M)) sum_k v_k e^(+2 pi j i k / M), in float32 and in the library's own
+ *     operation order (the bits are those of ofdm_dft_despread_frames with d_csi == NULL on that row).  A row whose v are all
+ *     0+0j is an erasure.
+ *  6. Weights per ROW, in double (a branch may miss a single row -- the zero rows of a guard-failed pattern -- so A may differ
+ *     from row to row of a segment).  Over the M entries of the row, with A the float32 value of step 4 widened: b = A/(A + 1.0),
+ *     e = 1.0/(A + 1.0); b = 0 and e = 1 for a symbol that is not combined.  beta = sum b / M, eps = sum e / M, w = beta/eps.
+ *     (The variance behind the transform is nu = mean(b^2) - beta^2 + mean(b e) = beta eps, so beta^2/nu = beta/eps; eps is summed
+ *     on its own and not taken as 1 - beta, which would cancel at high SNR.)  The two sums run in an order fixed by M alone,
+ *     without atomics: a row's beta and weight are the same bits wherever the row stands in its segment or the batch.  The row
+ *     is USABLE iff it is no erasure; beta, eps and w are finite and > 0; float(1/beta) and float(w) are finite.
+ *  7. Outputs.  u = x * float(1/beta) (float32, each product rounded); sym = u where the row is usable and u.re, u.im are finite,
+ *     else +0+0j.  llr and bits are functions of the STORED float32 sym and the row's weight = float(w) exactly as step 4 of the
+ *     DFT-spread contract above: llr = weight * d if the stored sym is not 0+0j and the product is finite and not zero, else +0;
+ *     bits = ofdm_demap's hard rule on the stored sym.  beta = float(beta) and weight, +0 both where the row is not usable.
+ *     comb = the v of step 4, before the transform.  No non-finite value leaves the call.
+ * Noise: OFDM_MRC_NOISE_GIVEN (HOST array h_noise_var[n_branch], each finite and > 0, read at call time) and OFDM_MRC_NOISE_SEG
+ * (DEVICE doubles d_sigma2[n_branch*n_seg] indexed by g; a value that is not finite or <= 0 is an erasure of that unit).
+ * OFDM_MRC_NOISE_EST is refused by both calls: the decision-directed estimate assumes constellation points per bin, which a
+ * spread signal does not have.  Decision-free sources for the SEG array are ofdm_rx_chan_noise_frames and
+ * ofdm_rx_chan_spread_frames (both per frame = per unit of a branch-major batch, in the units of the equalised symbols' noise:
+ * variance per bin of a signal of unit power per bin).
+ * comb is bit for bit the float32 restatement; sym agrees with fp64 on those float32 v to max|a-b|/max|b| < 1e-5; beta and weight
+ * within one float32 ulp (double sums rounded once); llr and bits are bit-exact functions of the device's own stored sym and
+ * weight.  The results depend on (B, M) and the row's data alone: the same bits in any batch, at any position of the row, at
+ * either alignment of every branch (8- or 16-byte bases) and on every call. */
+typedef struct ofdm_mrc_despread_out {   /* DEVICE pointers; NULL = not wanted */
+    float*   sym;      /* [n_seg][rows*M] complex64, dense */
+    float*   llr;      /* [n_seg][rows*M*bps] float32, dense */
+    uint8_t* bits;     /* hard bits of sym: [n_seg][rows*M*bps] one per byte, or /8 bytes packed MSB-first */
+    float*   beta;     /* [n_seg][rows] */
+    float*   weight;   /* [n_seg][rows] */
+    float*   comb;     /* [n_seg][rows*M] complex64, dense: the combined symbols before the transform */
+} ofdm_mrc_despread_out;
+/* Builds and caches the plan for M (ofdm_rx_reserve_despread's cache and capture rule), sizes the {c, t} table for n_branch*n_seg
+ * units and the |H|^2 rows of ofdm_rx_demod_frames_mrc_despread for n_branch*n_seg frames (n_branch*n_seg*num_data_bins floats,
+ * which ofdm_combine_despread_frames itself never reads: a caller of the stage alone pays them too, also where the stage grows
+ * its workspace on its own).  Grows, never shrinks; synchronises the device.  Call it before capturing; inside a capture a call that needs more is refused before anything is enqueued. */
+int ofdm_rx_reserve_mrc_despread(ofdm_rx* h, int32_t M, int32_t n_branch, int64_t n_seg);
+/* The stage on any device buffer (layout and steps above).  modulation 2, 4 or 6; bits_mode is read when out->bits is wanted.
+ * Asynchronous on `stream`: two launches (the combiner's table, then one fused launch that combines, transforms and writes),
+ * no host synchronisation and no allocation once ofdm_rx_reserve_mrc_despread covers the call.  n_seg == 0 or rows == 0 is a
+ * no-op.  Refusals are OFDM_ERR_INVALID with the reason in ofdm_last_error(), before anything is enqueued or any output
+ * touched: everything ofdm_combine_csi_frames and ofdm_dft_despread_frames refuse for the same argument (null handle, M not
+ * 2^a 3^b 5^c in 1 .. 4096, negative counts, n_branch outside 1..8, seg_stride < rows*M, csi_stride < M, BPSK, unknown noise_mode,
+ * the pointer the mode needs missing, a given variance not finite or <= 0, rho negative or not finite, bits wanted with
+ * OFDM_BITS_NONE or packed bits where M*bps % 8 != 0, `out` NULL or without any pointer, index range exceeded: n_branch*n_seg >
+ * 2^31, rows*M, n_branch*n_seg*seg_stride or n_branch*n_seg*csi_stride > 2^40, more than 2^31 - 1 workgroups), and
+ * OFDM_MRC_NOISE_EST.  The buffers must not overlap. */
+int ofdm_combine_despread_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int32_t M,
+                                 int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, int32_t modulation,
+                                 int32_t noise_mode, const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                 const ofdm_mrc_despread_out* out, void* stream);
+/* d_iq in the layout of ofdm_rx_demod_frames_mrc (frame f of branch b at index b*n_frames + f).  Runs ofdm_rx_demod_frames over
+ * the n_branch*n_frames frames (d_eq required; d_eq and d_tsr get the bits of that call), ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL)
+ * into the workspace, then the stage with rows = n_dsym, M = num_data_bins, rho = 1/snr_data of the handle's equaliser and
+ * modulation = cfg.modulation.  d_sigma2 (OFDM_MRC_NOISE_SEG) is [n_branch*n_frames].  Every check is made before anything is
+ * enqueued.  Returns n_dsym or a negative status. */
+int64_t ofdm_rx_demod_frames_mrc_despread(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames, int64_t frame_stride,
+                                          int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
+                                          const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                          const ofdm_mrc_despread_out* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ delay-window channel-estimate denoising
  * An extension the reference does not have.  The batch receiver's channel estimate is the least-squares (LS) estimate of ONE
  * Zadoff-Chu preamble symbol: as noisy as one received symbol.  A channel is shorter than the cyclic prefix, so nearly all of that

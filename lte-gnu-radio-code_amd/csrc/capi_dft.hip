@@ -1,6 +1,7 @@
 // capi_dft.hip -- DFT-spread OFDM on both handles: the plan cache, the transform precoder and the composite transmitter, the
 // despreading stage and the call that chains it behind ofdm_rx_demod_frames (definition: include/ofdm_mi355x.h, "DFT-spread
-// OFDM").
+// OFDM"), and the stage that combines B receive branches before it despreads, with its composite call
+// ("receive diversity for DFT-spread OFDM"): it lives here for the plan cache.
 #include "capi_internal.hpp"
 
 void dft_plans_free(DftPlanCache& c) {
@@ -138,6 +139,82 @@ int despread_launch(ofdm_rx* h, int slot, const float* d_sym, int64_t n_seg, int
     a.weight = out->weight;
     a.tab = h->ds_tab;
     HIP_TRY(launch_despread(a, s));
+    return OFDM_OK;
+}
+
+// ---- receiver, B branches combined before the transform
+bool mrc_despread_wanted(const ofdm_mrc_despread_out* o) { return o && (o->sym || o->llr || o->bits || o->beta || o->weight || o->comb); }
+// what the arguments alone decide: what ofdm_combine_csi_frames and ofdm_dft_despread_frames refuse for the same argument; "" = fine
+const char* mrc_despread_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int32_t M, int64_t seg_stride, int64_t csi_stride,
+                                  float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
+                                  int32_t bits_mode, const ofdm_mrc_despread_out* out) {
+    if (*dft_bad_size(M)) return dft_bad_size(M);
+    if (noise_mode == OFDM_MRC_NOISE_EST)
+        return "OFDM_MRC_NOISE_EST is refused (a spread signal has no constellation points per bin): pass OFDM_MRC_NOISE_GIVEN or "
+               "OFDM_MRC_NOISE_SEG";
+    const char* bad = mrc_bad_args(n_branch, n_seg, rows, M, seg_stride, csi_stride, rho, modulation, noise_mode, h_noise_var, d_sigma2,
+                                   false);
+    if (*bad) return bad;
+    if (!mrc_despread_wanted(out)) return "out is NULL or holds no pointer";
+    if (out->bits) {
+        if (!bits_mode_ok(bits_mode)) return "bits wanted: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+        if (bits_mode == OFDM_BITS_PACKED && (int64_t(M) * modulation) % 8 != 0) return "packed bits need M * bits per symbol % 8 == 0";
+    }
+    DftPlan pl;
+    dft_make_plan(M, pl);
+    if (!dft_rows_in_range(pl, rows, n_seg)) return "index range exceeded (more than 2^31 - 1 workgroups)";
+    return "";
+}
+// the plan for M, the table of the units and (frames > 0: the composite call) their |H|^2 rows, or a refusal inside a capture
+int mrc_despread_ensure(ofdm_rx* h, int32_t M, int32_t n_branch, int64_t n_seg, bool composite, hipStream_t s, const char* who,
+                        int* slot) {
+    const int64_t units = n_branch * n_seg;
+    *slot = dft_plan_find(h->dft, M);
+    if (*slot >= 0 && units * M <= h->cap_md_tab && (!composite || units <= h->cap_md_units)) return OFDM_OK;
+    int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_mrc_despread");
+    if (rc == OFDM_OK) rc = ofdm_rx_reserve_mrc_despread(h, M, n_branch, n_seg);
+    if (rc == OFDM_OK) *slot = dft_plan_find(h->dft, M);
+    return rc;
+}
+// d_sigma2 == null: the host array (OFDM_MRC_NOISE_GIVEN)
+int mrc_despread_launch(ofdm_rx* h, int slot, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t seg_stride,
+                        const float* d_csi, int64_t csi_stride, float rho, int32_t modulation, const double* h_noise_var,
+                        const double* d_sigma2, int32_t bits_mode, const ofdm_mrc_despread_out* out, hipStream_t s) {
+    const DftPlan& pl = h->dft.pl[slot];
+    MrcArgs t{};
+    t.n_branch = n_branch;
+    t.n_seg = n_seg;
+    t.rows = rows;
+    t.seg_stride = seg_stride;
+    t.row_len = pl.M;
+    t.seg_len = rows * pl.M;
+    t.csi = d_csi;
+    t.csi_stride = csi_stride;
+    t.rho = rho;
+    t.mod = modulation;
+    t.sigma2 = d_sigma2;
+    for (int b = 0; b < MRC_MAX_BRANCHES; ++b) t.noise_var[b] = (!d_sigma2 && b < n_branch) ? h_noise_var[b] : 0.0;
+    t.tab = h->md_tab;
+    HIP_TRY(launch_mrc_table(t, s));
+    MrcDespreadArgs a{};
+    a.pl = pl;
+    a.tw = h->dft.d_tw[slot];
+    a.sym = reinterpret_cast<const cf*>(d_sym);
+    a.n_branch = n_branch;
+    a.n_seg = n_seg;
+    a.rows = rows;
+    a.seg_stride = seg_stride;
+    a.groups_per_seg = (rows + pl.rows_per_group - 1) / pl.rows_per_group;
+    a.tab = h->md_tab;
+    a.mod = modulation;
+    a.bits_mode = bits_mode;
+    a.osym = reinterpret_cast<cf*>(out->sym);
+    a.llr = out->llr;
+    a.bits = out->bits;
+    a.beta = out->beta;
+    a.weight = out->weight;
+    a.comb = reinterpret_cast<cf*>(out->comb);
+    HIP_TRY(launch_mrc_despread(a, s));
     return OFDM_OK;
 }
 
@@ -286,6 +363,86 @@ int64_t ofdm_rx_demod_frames_despread(ofdm_rx* h, const float* d_iq, int64_t n_f
     HIP_TRY(launch_csi_frames(h->f_H, d.nfft, d.Kd, nullptr, d.Kd, n_frames, h->ds_a, d.Kd, s));
     const int rc = despread_launch(h, slot, d_eq, n_frames, n_dsym, n_dsym * d.Kd, h->ds_a, d.Kd, d.inv_snr_data, mod, noise_mode, noise_var,
                                    d_sigma2, bits_mode, out, s);
+    return rc != OFDM_OK ? rc : r;
+}
+
+int ofdm_rx_reserve_mrc_despread(ofdm_rx* h, int32_t M, int32_t n_branch, int64_t n_seg) {
+    const char* who = "ofdm_rx_reserve_mrc_despread";
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    if (*dft_bad_size(M)) return fail(OFDM_ERR_INVALID, "%s: %s", who, dft_bad_size(M));
+    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES) return fail(OFDM_ERR_INVALID, "%s: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES", who);
+    if (n_seg < 0) return fail(OFDM_ERR_INVALID, "%s: negative count", who);
+    if (n_seg > SOFT_MAX_N / n_branch) return fail(OFDM_ERR_INVALID, "%s: batch too large", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    int slot = dft_plan_find(h->dft, M);
+    if (slot < 0) {
+        const int rc = dft_plan_build(h, M, &slot);
+        if (rc != OFDM_OK) return rc;
+    }
+    HIP_TRY(mrc_despread_prepare());
+    const int64_t units = n_branch * n_seg;
+    if (units * M > h->cap_md_tab) {
+        const int rc = regrow(h, {{&h->cap_md_tab, units * M}}, ws_buf(&h->md_tab, size_t(units * M)));
+        if (rc != OFDM_OK) return rc;
+    }
+    if (units <= h->cap_md_units) return OFDM_OK;
+    return regrow(h, {{&h->cap_md_units, units}}, ws_buf(&h->md_a, size_t(units) * h->dev.Kd));
+}
+
+int ofdm_combine_despread_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int32_t M,
+                                 int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, int32_t modulation,
+                                 int32_t noise_mode, const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                 const ofdm_mrc_despread_out* out, void* stream) {
+    const char* who = "ofdm_combine_despread_frames";
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    const char* bad = mrc_despread_bad_args(n_branch, n_seg, rows, M, seg_stride, csi_stride, rho, modulation, noise_mode, h_noise_var,
+                                            d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    if (n_seg == 0 || rows == 0) return OFDM_OK;
+    if (!d_sym || !d_csi) return fail(OFDM_ERR_INVALID, "%s: null d_sym or d_csi", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = pick_stream(h, stream);
+    int slot = -1;
+    const int rc = mrc_despread_ensure(h, M, n_branch, n_seg, false, s, who, &slot);
+    if (rc != OFDM_OK) return rc;
+    return mrc_despread_launch(h, slot, d_sym, n_branch, n_seg, rows, seg_stride, d_csi, csi_stride, rho, modulation, h_noise_var,
+                               noise_mode == OFDM_MRC_NOISE_SEG ? d_sigma2 : nullptr, bits_mode, out, s);
+}
+
+int64_t ofdm_rx_demod_frames_mrc_despread(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames, int64_t frame_stride,
+                                          int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
+                                          const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                          const ofdm_mrc_despread_out* out, void* stream) {
+    const char* who = "ofdm_rx_demod_frames_mrc_despread";
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, who);
+    if (open != OFDM_OK) return open;
+    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES)
+        return fail(OFDM_ERR_INVALID, "%s: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES", who);
+    if (n_frames > SOFT_MAX_N / n_branch) return fail(OFDM_ERR_INVALID, "%s: batch too large (n_branch * n_frames > 2^31)", who);
+    if (!d_eq) return fail(OFDM_ERR_INVALID, "%s: the stage needs d_eq (it reads it)", who);
+    const RxDev& d = h->dev;
+    const int mod = h->cfg.modulation;
+    const int64_t units = n_branch * n_frames;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
+    // the checks of the stages, made here first so that a bad call enqueues nothing
+    const char* bad = demod_bad_args(d, units, n_dsym, nullptr, OFDM_BITS_NONE);
+    if (!*bad)
+        bad = mrc_despread_bad_args(n_branch, n_frames, n_dsym, d.Kd, n_dsym * d.Kd, d.Kd, d.inv_snr_data, mod, noise_mode, h_noise_var,
+                                    d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    hipStream_t s = pick_stream(h, stream);
+    const bool run = n_frames > 0 && n_dsym > 0;
+    int slot = -1;
+    if (run) {                                              // grow first: nothing is enqueued unless the whole call can run
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        const int rc = mrc_despread_ensure(h, d.Kd, n_branch, n_frames, true, s, who, &slot);
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t r = ofdm_rx_demod_frames(h, d_iq, units, frame_stride, frame_len, d_eq, nullptr, OFDM_BITS_NONE, d_tsr, stream);
+    if (r < 0 || !run) return r;
+    HIP_TRY(launch_csi_frames(h->f_H, d.nfft, d.Kd, nullptr, d.Kd, units, h->md_a, d.Kd, s));
+    const int rc = mrc_despread_launch(h, slot, d_eq, n_branch, n_frames, n_dsym, n_dsym * d.Kd, h->md_a, d.Kd, d.inv_snr_data, mod,
+                                       h_noise_var, noise_mode == OFDM_MRC_NOISE_SEG ? d_sigma2 : nullptr, bits_mode, out, s);
     return rc != OFDM_OK ? rc : r;
 }
 

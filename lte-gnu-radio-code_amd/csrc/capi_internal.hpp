@@ -150,6 +150,11 @@ struct ofdm_rx {
     float4* ds_tab = nullptr;            // [n_seg] {float(1/beta), weight, beta, usable} (DespreadArgs)
     float* ds_a = nullptr;               // [n_seg][Kd] |H|^2 rows of ofdm_rx_demod_frames_despread
     int64_t cap_ds_seg = 0;
+    // ---- receive diversity for DFT-spread OFDM (ofdm_rx_reserve_mrc_despread); the plans are those above
+    float2* md_tab = nullptr;            // [n_branch*n_seg][M] {c, t} (mrc_table_kernel)
+    int64_t cap_md_tab = 0;
+    float* md_a = nullptr;               // [n_branch*n_frames][Kd] |H|^2 rows of ofdm_rx_demod_frames_mrc_despread
+    int64_t cap_md_units = 0;
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;
@@ -257,6 +262,10 @@ struct ofdm_tx {
 // capi_dft.hip: frees the tables of a handle's plans (the destroys)
 #pragma GCC visibility push(hidden)
 void dft_plans_free(DftPlanCache& c);
+// capi_mrc.hip: what ofdm_combine_csi_frames checks about its arguments alone; "" = fine
+const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
+                         float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
+                         bool composite);
 #pragma GCC visibility pop
 
 namespace {

@@ -8,8 +8,10 @@ namespace {
 static_assert(OFDM_MRC_MAX_BRANCHES == MRC_MAX_BRANCHES, "the header's branch limit is the kernels'");
 bool mrc_wanted(const ofdm_mrc_out* o) { return o && (o->llr || o->sym || o->weight); }
 bool mrc_units_ok(int32_t n_branch, int64_t n_seg) { return n_seg <= SOFT_MAX_N / n_branch; }
-// what the arguments alone decide (no read of the handle, no device access); "" = fine.  given_only: the composite call, which
-// takes the variances from the host or estimates them.
+}  // namespace
+
+// what the arguments alone decide (no read of the handle, no device access); "" = fine.  composite: the call that takes
+// the variances from the host or estimates them.  Declared in capi_internal.hpp: capi_dft.hip makes the same checks.
 const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
                          float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
                          bool composite) {
@@ -38,6 +40,8 @@ const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t 
         return "index range exceeded (batch beyond the kernels' index range)";
     return "";
 }
+
+namespace {
 // grows the workspace; refuses inside a stream capture (growing synchronises and allocates)
 int mrc_ensure(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, bool composite, hipStream_t s,
                const char* who) {

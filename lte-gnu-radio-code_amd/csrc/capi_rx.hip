@@ -18,7 +18,7 @@ int ofdm_rx_destroy(ofdm_rx* h) {
              &h->s_ysc, &h->d_trial_m, &h->d_trial_d, &h->d_partial, &h->f_tsr, &h->f_H, &h->f_gain, &h->f_htime, &h->d_scan_g,
              &h->d_seg_state, &h->d_work, &h->f_seg_partial, &h->p_idx, &h->p_k, &h->p_src, &h->f_usum, &h->t_ws, &h->c_part_e,
              &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail, &h->f_spread, &h->a_part_d, &h->a_part_a0, &h->a_part_q, &h->a_part_n,
-             &h->k_H, &h->k_flag, &h->k_nb, &h->k_rtsr, &h->k_eq, &h->ds_tab, &h->ds_a);
+             &h->k_H, &h->k_flag, &h->k_nb, &h->k_rtsr, &h->k_eq, &h->ds_tab, &h->ds_a, &h->md_tab, &h->md_a);
     dft_plans_free(h->dft);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);

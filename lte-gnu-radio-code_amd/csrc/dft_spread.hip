@@ -12,87 +12,10 @@
 // two barriers each, and writes from LDS in natural order (16-byte stores where aligned).  The arithmetic of an element does
 // not depend on the load or store width nor on the row's place in the batch, so its bits depend on (M, the row's data) alone.
 // Every float32 product, sum and quotient of the epilogue is rounded on its own (contraction off).
-#include "ofdm_launch.hpp"
-#include "dft_mixed.hpp"
-#include "soft_device.hpp"
+#include "dft_rows_device.hpp"
 #include "demap_hard.hpp"
 
 namespace ofdm {
-
-namespace {
-
-struct RowRef {
-    int r, i;                // local row, entry
-};
-__device__ __forceinline__ RowRef row_of(int e, int M) {
-    const int r = int(unsigned(e) / unsigned(M));
-    return RowRef{r, e - r * M};
-}
-
-// Elements 0 .. cnt-1 of the group's rows (contiguous at src) into LDS.  MASK: step 1 of the despread contract (csi: the
-// segment's row of channel powers, or null) and the rows that hold anything but zeros marked in row_nz.  CONJ: conjugated.
-template <bool MASK, bool CONJ>
-__device__ __forceinline__ void stage_in(const DftPlan& pl, const cf* src, int cnt, cf* lds, const float* csi, int* row_nz) {
-    const bool wide = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-    auto put = [&](int e, cf z) {
-        const RowRef at = row_of(e, pl.M);
-        if constexpr (MASK) {
-            bool ok = soft_finite(z.x) && soft_finite(z.y);
-            if (csi) {
-                const float a = csi[at.i];
-                ok = ok && soft_finite(a) && a > 0.f;
-            }
-            if (!ok) z = cf{0.f, 0.f};
-            if (z.x != 0.f || z.y != 0.f) row_nz[at.r] = 1;
-        }
-        if constexpr (CONJ) z.y = -z.y;
-        lds[at.r * pl.row_elems + dft_phys(at.i, pl.pad)] = z;
-    };
-    for (int e = 2 * int(threadIdx.x); e < cnt; e += 2 * DFT_THREADS) {
-        const bool two = e + 1 < cnt;
-        if (wide && two) {
-            const float4 v = load_stream16(reinterpret_cast<const float*>(src + e));
-            put(e, cf{v.x, v.y});
-            put(e + 1, cf{v.z, v.w});
-        } else {
-            const float2 v0 = load_stream8(reinterpret_cast<const float*>(src + e));
-            put(e, cf{v0.x, v0.y});
-            if (two) {
-                const float2 v1 = load_stream8(reinterpret_cast<const float*>(src + e + 1));
-                put(e + 1, cf{v1.x, v1.y});
-            }
-        }
-    }
-}
-
-// the passes of the nrows rows in LDS; every lane of the workgroup calls this.  CAP >= pl.M (DFT_SMALL_M or DFT_MAX_M)
-template <int CAP>
-__device__ __forceinline__ void dft_rows_in_lds(const DftPlan& pl, const cf* tw, cf* lds, int nrows) {
-    const int r = int(threadIdx.x) / pl.lanes, lane = int(threadIdx.x) - r * pl.lanes;
-    const bool active = r < nrows;
-    cf* row = lds + r * pl.row_elems;
-    cf v[DFT_MAX_REGS];
-    int s = 1;
-    for (int p = 0; p < pl.n_pass; ++p) {
-        const int R = pl.radix[p];
-        if (active) dft_pass_load_rt<CAP>(pl, R, s, lane, row, tw, v);
-        __syncthreads();
-        if (active) dft_pass_store_rt<CAP>(pl, R, s, lane, row, v);
-        __syncthreads();
-        s *= R;
-    }
-}
-
-__device__ __forceinline__ void store_sym_pair(cf* dst, int e, bool two, bool wide, cf u0, cf u1) {
-    if (wide && two) {
-        store_stream16(reinterpret_cast<float*>(dst + e), float4{u0.x, u0.y, u1.x, u1.y});
-    } else {
-        store_stream8(reinterpret_cast<float*>(dst + e), float2{u0.x, u0.y});
-        if (two) store_stream8(reinterpret_cast<float*>(dst + e + 1), float2{u1.x, u1.y});
-    }
-}
-
-}  // namespace
 
 struct DftRowsArgs {
     DftPlan pl;

@@ -224,6 +224,32 @@ struct DespreadArgs {
 hipError_t launch_despread(const DespreadArgs& a, hipStream_t s);
 hipError_t dft_spread_prepare();         // loads the kernels (before a stream capture)
 
+// ---- receive diversity for DFT-spread OFDM (mrc_despread.hip; contract: include/ofdm_mi355x.h, "receive diversity for DFT-spread
+// OFDM").  The {c, t} table of the combiner alone (rx_mrc.hip: a reads n_branch, n_seg, row_len, csi,
+// csi_stride, rho, noise_var / sigma2, tab), then one workgroup per (output segment, group of pl.rows_per_group rows): the
+// branches combined per bin into LDS, the inverse transform, the row's own weights, the epilogue of the despreading stage.
+hipError_t launch_mrc_table(const MrcArgs& a, hipStream_t s);
+hipError_t mrc_table_prepare();          // loads mrc_table_kernel
+struct MrcDespreadArgs {
+    DftPlan pl;
+    const cf* tw;
+    const cf* sym;           // unit g = b*n_seg + s at sym + g*seg_stride
+    int n_branch;
+    int64_t n_seg, rows, seg_stride;      // complex items
+    int64_t groups_per_seg;  // ceil(rows / pl.rows_per_group)
+    const float2* tab;       // [n_branch*n_seg][M] {c, t} of launch_mrc_table
+    int mod;                 // 2, 4, 6 (read when llr or bits is wanted)
+    int bits_mode;           // ofdm_bits_mode
+    cf* osym;                // [n_seg][rows*M], or null
+    float* llr;              // [n_seg][rows*M*mod], or null
+    uint8_t* bits;           // hard bits of osym, or null
+    float* beta;             // [n_seg][rows], or null
+    float* weight;           // [n_seg][rows], or null
+    cf* comb;                // [n_seg][rows*M] the combined symbols before the transform, or null
+};
+hipError_t launch_mrc_despread(const MrcDespreadArgs& a, hipStream_t s);   // the caller has checked the arguments and the grid
+hipError_t mrc_despread_prepare();       // loads the kernels of both launches (before a stream capture)
+
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
 // consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.

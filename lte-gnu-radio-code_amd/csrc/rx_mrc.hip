@@ -281,6 +281,16 @@ static void launch_mrc_llr(const MrcArgs& a, bool more, unsigned grid, hipStream
         hipLaunchKernelGGL((mrc_llr_kernel<MOD, false>), dim3(grid), dim3(256), 0, s, a);
 }
 
+// The table alone, for the stage that despreads what it combines (mrc_despread.hip).  The caller has sized the table.
+hipError_t launch_mrc_table(const MrcArgs& a, hipStream_t s) {
+    const int64_t entries = int64_t(a.n_branch) * a.n_seg * a.row_len;
+    if (entries <= 0) return hipSuccess;
+    const unsigned gt = unsigned(std::min<int64_t>((entries + 255) / 256, MRC_GRID_CAP));
+    hipLaunchKernelGGL(mrc_table_kernel, dim3(gt), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t mrc_table_prepare() { return load_kernels(mrc_table_kernel); }
+
 // The caller has checked the arguments and sized the table.
 hipError_t launch_combine_mrc(const MrcArgs& a, hipStream_t s) {
     if (a.n_seg <= 0 || a.seg_len <= 0 || a.n_branch <= 0) return hipSuccess;

@@ -104,6 +104,12 @@ class MrcOut(C.Structure):
     _fields_ = [("llr", C.c_void_p), ("sym", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class MrcDespreadOut(C.Structure):
+    """ofdm_mrc_despread_out: device pointers of the stage that combines B branches and despreads (None = not wanted)."""
+    _fields_ = [("sym", C.c_void_p), ("llr", C.c_void_p), ("bits", C.c_void_p), ("beta", C.c_void_p), ("weight", C.c_void_p),
+                ("comb", C.c_void_p)]
+
+
 class TrackOut(C.Structure):
     """ofdm_track_out: device pointers of the channel-tracking stage (None = not wanted)."""
     _fields_ = [("eq", C.c_void_p), ("bits", C.c_void_p), ("csi", C.c_void_p), ("H_pat", C.c_void_p), ("takes", C.c_void_p)]
@@ -237,6 +243,13 @@ PROTOTYPES = {
     "ofdm_rx_demod_frames_mrc": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
                                              C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(MrcOut), C.c_void_p,
                                              C.c_void_p]),
+    "ofdm_rx_reserve_mrc_despread": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),
+    "ofdm_combine_despread_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                               C.c_void_p, C.c_int32, C.POINTER(MrcDespreadOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_mrc_despread": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                                      C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_int32,
+                                                      C.POINTER(MrcDespreadOut), C.c_void_p]),
     "ofdm_tbcc_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
     "ofdm_tx_tbcc_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_int64, C.c_void_p]),

@@ -468,6 +468,51 @@ class RxEngine(_Handle):
                                                            MRC_NOISE_GIVEN if given else MRC_NOISE_EST, nv, C.byref(out),
                                                            ptr(d_sigma2), ptr(stream))))
 
+    # ---- receive diversity for DFT-spread OFDM: B branches combined per bin, then despread (include/ofdm_mi355x.h) ---------------
+    @staticmethod
+    def _mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb):
+        return _lib.MrcDespreadOut(_addr(d_sym_out), _addr(d_llr), _addr(d_bits), _addr(d_beta), _addr(d_weight), _addr(d_comb))
+
+    def reserve_mrc_despread(self, M: int, n_branch: int, n_seg: int = 0):
+        """ofdm_rx_reserve_mrc_despread: the plan for M, the table of n_branch*n_seg units and the |H|^2 rows of
+        demod_frames_mrc_despread for as many frames (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_mrc_despread(self._h, int(M), int(n_branch), int(n_seg)))
+
+    def combine_despread_frames(self, d_sym, n_branch, n_seg, rows, M, seg_stride, d_csi, csi_stride, rho, modulation,
+                                noise_var=None, d_sigma2=None, d_sym_out=None, d_llr=None, d_bits=None, bits_mode=BITS_NONE,
+                                d_beta=None, d_weight=None, d_comb=None, stream=None):
+        """ofdm_combine_despread_frames: branch b of segment s is the unit g = b*n_seg + s, `rows` rows of M equalised complex64
+        symbols at d_sym + g*seg_stride with the channel powers d_csi[g*csi_stride + k].  Exactly one of noise_var (n_branch
+        numbers, one variance per branch) and d_sigma2 (device, [n_branch*n_seg] float64, one per unit) is given; their absolute
+        level matters.  Outputs per segment: sym [rows*M] complex64, llr [rows*M*bps] float32 (positive favours bit 0), hard
+        bits, beta and weight [rows] float32 (one per ROW), comb [rows*M] complex64 (the combined symbols before the transform)."""
+        if (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("combine_despread_frames: give exactly one of noise_var and d_sigma2")
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
+        check(self.lib.ofdm_combine_despread_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(M),
+                                                    int(seg_stride), ptr(d_csi), int(csi_stride), float(rho), _mod_bits(modulation),
+                                                    MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2), int(bits_mode),
+                                                    C.byref(out), ptr(stream)))
+
+    def demod_frames_mrc_despread(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_sigma2=None,
+                                  d_sym_out=None, d_llr=None, d_bits=None, bits_mode=BITS_NONE, d_beta=None, d_weight=None,
+                                  d_comb=None, d_tsr=None, stream=None) -> int:
+        """demod_frames over the n_branch*n_frames frames of d_iq (frame f of branch b at index b*n_frames + f), then
+        csi_frames(CSI_ROWS_ALL) into the workspace and combine_despread_frames over d_eq with one segment per frame (n_dsym rows
+        of M = Kd symbols, the handle's rho and modulation).  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device,
+        [n_branch*n_frames] float64).  Returns n_dsym."""
+        if (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("demod_frames_mrc_despread: give exactly one of noise_var and d_sigma2")
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
+        return int(check(self.lib.ofdm_rx_demod_frames_mrc_despread(self._h, ptr(d_iq), int(n_branch), int(n_frames),
+                                                                    int(frame_stride), int(frame_len), ptr(d_eq), ptr(d_tsr),
+                                                                    MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2),
+                                                                    int(bits_mode), C.byref(out), ptr(stream))))
+
     # ---- delay-window denoising of the LS channel estimate (include/ofdm_mi355x.h) ----------------------------------------------
     def set_chan_window(self, pre: int, post: int):
         """ofdm_rx_set_chan_window: while (pre, post) != (0, 0), demod_frames -- and every demod_frames_* call -- refines its
