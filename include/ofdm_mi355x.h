@@ -539,6 +539,80 @@ int64_t ofdm_rx_demod_frames_mrc_despread(ofdm_rx* h, const float* d_iq, int32_t
                                           const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
                                           const ofdm_mrc_despread_out* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------ multi-user allocations of DFT-spread OFDM
+ * An extension the reference does not have: the multiple access of SC-FDMA.  Several users share a symbol; each occupies its own
+ * contiguous run of subcarriers, with its own DFT size, its own modulation and, behind the transform, its own gain beta and LLR
+ * weight.  Nothing changes in front of the stage: the channel estimate, the equaliser and ofdm_rx_csi_frames work per bin.  This
+ * text is the definition; tests/dft_alloc_ref.py restates it in NumPy (a loop over the allocations around tests/dft_spread_ref.py).
+ *
+ * An ALLOCATION is (start, M, modulation): entries start .. start+M-1 of a row of row_len entries.  M is any size
+ * ofdm_dft_size_ok accepts, modulation is 2, 4 or 6 bits per symbol and is read by the receiver only (the transmitter's mapper
+ * keeps the handle's single modulation).  An ALLOCATION SET is a list of up to OFDM_MAX_ALLOCS allocations that do not overlap.
+ * The list need not be sorted and may leave gaps; its order is the caller's and fixes the order of the outputs.
+ *
+ * The contract in one sentence: for every allocation u the stage writes exactly -- bit for bit, in every output, beta and weight
+ * included -- what ofdm_dft_despread_frames writes for M = M_u and modulation = mod_u when given a dense copy of columns
+ * start_u .. start_u+M_u-1 of every row, the same columns of d_csi, the same rho and the same noise.  Steps 1-4 of the DFT-spread
+ * contract above apply per allocation, word for word.  Entries of a row outside every allocation are never read for data.  With
+ * OFDM_DESPREAD_NOISE_SEG the one sigma2 of a segment is shared by all its allocations: it is the receiver's noise, not a user's.
+ * The transmit precoder likewise replaces allocation u of every row by what ofdm_tx_dft_spread gives on the gathered columns, bit
+ * for bit, and writes every entry outside all allocations as +0+0j (nothing is sent there).
+ *
+ * Outputs are allocation-major and dense: block u of sym is [n_seg][rows*M_u] complex64 at symbol offset
+ * n_seg*rows*sum_{v<u} M_v; llr and bits likewise with M_v*bps_v (packed bits: that count / 8, and M_u*bps_u % 8 == 0 for every
+ * u); beta and weight are [n_alloc][n_seg].  ofdm_alloc_layout returns these offsets. */
+#define OFDM_MAX_ALLOCS 32
+/* Host call, no GPU needed: the offsets of the blocks in sym (complex items), llr (floats) and bits (bytes; all 0 with
+ * OFDM_BITS_NONE) and totals[3] = the sizes of the three outputs in the same units.  n_alloc in 1 .. OFDM_MAX_ALLOCS, sizes and
+ * modulations as above, counts >= 0, packed bits only where every M*bps % 8 == 0: else OFDM_ERR_INVALID.  Output pointers may be
+ * NULL. */
+int ofdm_alloc_layout(int32_t n_alloc, const int32_t* M, const int32_t* mod, int64_t n_seg, int64_t rows, int32_t bits_mode,
+                      int64_t* sym_off, int64_t* llr_off, int64_t* bits_off, int64_t* totals);
+/* The allocation set of a handle, from HOST arrays that are copied; n_alloc == 0 clears it.  Synchronises the device, like
+ * ofdm_*_set_pilots (call it outside a capture; a graph captured with an earlier set must not be replayed afterwards).  The set
+ * owns what its kernels read: its plans, their twiddle tables (built as those of the single-M calls: fp64, rounded once) and the
+ * descriptor table on the device.  It does not live in the 8-slot plan cache: no later reserve or single-M call invalidates it
+ * and it evicts nothing.  Refused with OFDM_ERR_INVALID and the reason in ofdm_last_error(), the previous set staying in force:
+ * null handle, n_alloc outside 0 .. OFDM_MAX_ALLOCS, null arrays with n_alloc > 0, start < 0, an M that is not ok,
+ * start + M > 4096, two allocations that overlap, a modulation that is not 2, 4 or 6. */
+int ofdm_rx_set_allocations(ofdm_rx* h, int32_t n_alloc, const int32_t* h_start, const int32_t* h_M, const int32_t* h_mod);
+int ofdm_tx_set_allocations(struct ofdm_tx* h, int32_t n_alloc, const int32_t* h_start, const int32_t* h_M);
+/* Sizes the [n_alloc][n_seg] table of the stage for the set in force and the |H|^2 rows of ofdm_rx_demod_frames_despread_alloc
+ * (n_seg frames), and loads the kernels.  Grows, never shrinks; synchronises the device.  Needs a set.  After it the stage
+ * enqueues without host synchronisation or allocation and can be captured and replayed; inside a capture a call that needs more
+ * is refused before anything is enqueued. */
+int ofdm_rx_reserve_despread_alloc(ofdm_rx* h, int64_t n_seg);
+/* The stage.  Segment s is `rows` rows of row_len complex64 at d_sym + s*seg_stride; d_csi + s*csi_stride holds row_len channel
+ * powers (d_csi == NULL: the plain inverse transforms); rho, the noise modes and `out` as ofdm_dft_despread_frames, the outputs in
+ * the allocation-major layout above.  Asynchronous on `stream`.  The number of launches does not grow with n_alloc: one for the
+ * table, then at most one per (M <= 2048 or not, modulation) pair present in the set -- one per size class when neither llr nor
+ * bits is wanted.  Refused before anything is enqueued or any output touched: everything ofdm_dft_despread_frames refuses for
+ * the same argument (per allocation), no allocation set, row_len < max(start + M), seg_stride < rows*row_len, csi_stride <
+ * row_len, packed bits with an allocation whose bits do not fill bytes, index ranges (rows*row_len, the per-allocation rows*M_u,
+ * n_seg*seg_stride, more than 2^31 - 1 workgroups), out->sym == d_sym (the layouts differ), growth inside a stream capture. */
+int ofdm_dft_despread_alloc_frames(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride,
+                                   const float* d_csi, int64_t csi_stride, float rho, int32_t noise_mode, double noise_var,
+                                   const double* d_sigma2, int32_t bits_mode, const ofdm_despread_out* out, void* stream);
+/* ofdm_rx_demod_frames_despread with the stage above in place of the single transform: ofdm_rx_demod_frames (d_eq required), then
+ * ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL) into the workspace, then the stage with row_len = num_data_bins, one segment per frame
+ * and rho from the handle.  Follows ofdm_rx_set_chan_window and ofdm_rx_set_chan_average like every ofdm_rx_demod_frames_* call.
+ * Every check is made before anything is enqueued.  Returns n_dsym or a negative status. */
+int64_t ofdm_rx_demod_frames_despread_alloc(ofdm_rx* h, const float* d_iq, int64_t n_frames, int64_t frame_stride, int64_t frame_len,
+                                            float* d_eq, int32_t* d_tsr, int32_t noise_mode, double noise_var, const double* d_sigma2,
+                                            int32_t bits_mode, const ofdm_despread_out* out, void* stream);
+/* Transform precoder over the transmitter's set: n_rows rows of row_len complex64 in, the same layout out, d_out == d_sym
+ * allowed.  One launch per size class present (M <= 2048 or not).  Refused: no set, row_len < max(start + M), negative or
+ * out-of-range counts, null buffers. */
+int ofdm_tx_dft_spread_alloc(struct ofdm_tx* h, const float* d_sym, int64_t n_rows, int64_t row_len, float* d_out, void* stream);
+/* Sizes the workspace of ofdm_tx_modulate_frames_alloc for n_rows data symbols (the buffers of ofdm_tx_reserve_spread, without a
+ * plan) and loads the kernels.  Grows, never shrinks; synchronises the device. */
+int ofdm_tx_reserve_spread_alloc(struct ofdm_tx* h, int64_t n_rows);
+/* ofdm_tx_modulate_frames_spread with ofdm_tx_dft_spread_alloc (row_len = num_data_bins) in place of the single transform.  The
+ * bits of entries outside every allocation are read and discarded.  Refused if there is no set or it does not fit
+ * num_data_bins. */
+int64_t ofdm_tx_modulate_frames_alloc(struct ofdm_tx* h, const uint8_t* d_bits, int32_t bits_mode, int64_t n_frames, int32_t n_sym,
+                                      float* d_iq, int64_t frame_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------ delay-window channel-estimate denoising
  * An extension the reference does not have.  The batch receiver's channel estimate is the least-squares (LS) estimate of ONE
  * Zadoff-Chu preamble symbol: as noisy as one received symbol.  A channel is shorter than the cyclic prefix, so nearly all of that

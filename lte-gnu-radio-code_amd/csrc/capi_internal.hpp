@@ -54,6 +54,18 @@ struct DftPlanCache {
     int n = 0;
 };
 
+// Multi-user allocations of DFT-spread OFDM (capi_dft.hip, ofdm_*_set_allocations): the set owns what its kernels read -- one
+// buffer with the twiddle tables of its sizes and the descriptor table -- and does not touch the plan cache above.
+struct DftAllocSet {
+    int n = 0;
+    int max_end = 0;                     // max(start + M)
+    DftAllocDesc h[DFT_MAX_ALLOCS] = {}; // the host copy of d_set (tw: device pointers into d_tw)
+    DftAllocDesc* d_set = nullptr;       // [n]
+    cf* d_tw = nullptr;                  // the tables of the distinct sizes, one after the other
+    int n_gap = 0;                       // runs of entries below max_end that no allocation covers, ascending
+    int gap_start[DFT_MAX_ALLOCS + 1] = {}, gap_len[DFT_MAX_ALLOCS + 1] = {};
+};
+
 struct ofdm_rx {
     ofdm_rx_cfg cfg{};
     hipStream_t stream = nullptr;
@@ -155,6 +167,12 @@ struct ofdm_rx {
     int64_t cap_md_tab = 0;
     float* md_a = nullptr;               // [n_branch*n_frames][Kd] |H|^2 rows of ofdm_rx_demod_frames_mrc_despread
     int64_t cap_md_units = 0;
+    // ---- multi-user allocations of DFT-spread OFDM (ofdm_rx_set_allocations, ofdm_rx_reserve_despread_alloc)
+    DftAllocSet alloc{};
+    float4* da_tab = nullptr;            // [n_alloc][n_seg] {float(1/beta), weight, beta, usable}
+    int64_t cap_da_tab = 0;              // entries
+    float* da_a = nullptr;               // [n_seg][Kd] |H|^2 rows of ofdm_rx_demod_frames_despread_alloc
+    int64_t cap_da_seg = 0;
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;
@@ -257,11 +275,13 @@ struct ofdm_tx {
     cf* sp_grid = nullptr;               // [rows][nfft]
     cf* sp_time = nullptr;               // [rows][L]
     int64_t cap_sp_rows = 0;
+    DftAllocSet alloc{};                 // ofdm_tx_set_allocations
 };
 
 // capi_dft.hip: frees the tables of a handle's plans (the destroys)
 #pragma GCC visibility push(hidden)
 void dft_plans_free(DftPlanCache& c);
+void dft_alloc_free(DftAllocSet& a);     // capi_dft.hip: frees a handle's allocation set (the destroys)
 // capi_mrc.hip: what ofdm_combine_csi_frames checks about its arguments alone; "" = fine
 const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
                          float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,

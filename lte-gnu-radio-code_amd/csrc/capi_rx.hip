@@ -20,6 +20,8 @@ int ofdm_rx_destroy(ofdm_rx* h) {
              &h->c_part_n, &h->c_tab, &h->c_a, &h->m_tab, &h->m_sigma2, &h->f_tail, &h->f_spread, &h->a_part_d, &h->a_part_a0, &h->a_part_q, &h->a_part_n,
              &h->k_H, &h->k_flag, &h->k_nb, &h->k_rtsr, &h->k_eq, &h->ds_tab, &h->ds_a, &h->md_tab, &h->md_a);
     dft_plans_free(h->dft);
+    dft_alloc_free(h->alloc);
+    free_dev(&h->da_tab, &h->da_a);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);

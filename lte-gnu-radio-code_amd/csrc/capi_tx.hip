@@ -10,6 +10,7 @@ int ofdm_tx_destroy(ofdm_tx* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     free_dev(&h->d_tw, &h->d_zc, &h->d_sync_time, &h->d_pilots, &h->tb_ws, &h->sp_sym, &h->sp_grid, &h->sp_time);
     dft_plans_free(h->dft);
+    dft_alloc_free(h->alloc);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return OFDM_OK;

@@ -250,6 +250,55 @@ struct MrcDespreadArgs {
 hipError_t launch_mrc_despread(const MrcDespreadArgs& a, hipStream_t s);   // the caller has checked the arguments and the grid
 hipError_t mrc_despread_prepare();       // loads the kernels of both launches (before a stream capture)
 
+// ---- multi-user allocations of DFT-spread OFDM (dft_alloc.hip; contract: include/ofdm_mi355x.h, "multi-user allocations";
+// DESIGN.md 9.2.17).  An allocation set is a table of DftAllocDesc on the device, owned by the handle; a launch serves the
+// allocations of one class (CAP, modulation) and finds its allocation from blockIdx.x through DftAllocClass::end.
+constexpr int DFT_MAX_ALLOCS = 32;
+struct DftAllocDesc {
+    DftPlan pl;
+    const cf* tw;            // [M], the set's own table
+    int start, mod;          // first entry of the row; bits per symbol (receiver)
+    int64_t sym_before;      // sum of M_v, v < u: block u of the dense outputs starts n_seg*rows*sym_before symbols in
+    int64_t bit_before;      // sum of M_v*mod_v, v < u
+};
+struct DftAllocClass {       // by value in the kernel arguments: it depends on the call's rows and n_seg
+    int n;                   // allocations of this launch
+    uint8_t idx[DFT_MAX_ALLOCS];     // their places in the set
+    unsigned end[DFT_MAX_ALLOCS];    // workgroups up to and including allocation k (a prefix sum of n_seg * groups)
+};
+struct DespreadAllocArgs {
+    const DftAllocDesc* set;
+    int n_alloc;
+    const cf* sym;           // segment s: rows rows of row_len at sym + s*seg_stride
+    int64_t n_seg, rows, row_len, seg_stride;
+    const float* csi;        // [n_seg][csi_stride] |H|^2 per entry of the row, or null
+    int64_t csi_stride;
+    float rho;
+    int noise_mode;
+    double noise_var;
+    const double* sigma2;    // SEG: [n_seg], shared by the allocations of a segment
+    int bits_mode;
+    cf* osym;                // allocation-major dense blocks, or null
+    float* llr;
+    uint8_t* bits;
+    float* beta;             // [n_alloc][n_seg], or null
+    float* weight;
+    float4* tab;             // [n_alloc][n_seg] workspace {float(1/beta), weight, beta, usable}
+};
+// h_set: the host copy of the table (plans, modulations).  The caller has checked the arguments and every grid.
+hipError_t launch_despread_alloc(const DespreadAllocArgs& a, const DftAllocDesc* h_set, hipStream_t s);
+struct DftAllocRowsArgs {
+    const DftAllocDesc* set;
+    const cf* in;            // [n_rows][row_len]
+    cf* out;                 // [n_rows][row_len], may be `in`
+    int64_t n_rows, row_len;
+    int n_gap;               // runs of entries outside every allocation, written as +0+0j
+    int gap_start[DFT_MAX_ALLOCS + 1], gap_len[DFT_MAX_ALLOCS + 1];
+    unsigned zero_groups;    // workgroups behind the class's own that write the gaps (first launch only)
+};
+hipError_t launch_dft_alloc_rows(DftAllocRowsArgs a, const DftAllocDesc* h_set, int n_alloc, hipStream_t s);
+hipError_t dft_alloc_prepare();          // loads the kernels (before a stream capture)
+
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
 // consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.

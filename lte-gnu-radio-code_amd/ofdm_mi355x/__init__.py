@@ -4,7 +4,7 @@ from ._lib import (BITS_NONE, BITS_PACKED, BITS_UNPACKED, COMPAT_RXOFDM, COMPAT_
                    DESPREAD_NOISE_SEG, LIB_PATH, MRC_NOISE_EST, MRC_NOISE_GIVEN,
                    MRC_NOISE_SEG, OfdmError, OfdmLibraryError, PILOT_CPE,
                    PILOT_CPE_SLOPE, TRACK_HOLD, TRACK_LINEAR, load)
-from .engine import (DeviceBuffer, FoEngine, RxEngine, TrkEngine, TxEngine, bins_p, count_bit_errors, crc_bits,  # noqa: F401
+from .engine import (DeviceBuffer, FoEngine, RxEngine, TrkEngine, TxEngine, alloc_layout, bins_p, count_bit_errors, crc_bits,  # noqa: F401
                      crc_compute, crc_compute_long, dft_plan_info, dft_size_ok, gold_bits, tb_geometry, tbcc_blocks, tbcc_rm_blocks, turbo_blocks,
                      turbo_k_next, turbo_qpp_check, turbo_rm_blocks, turbo_rm_info, zadoff_chu)
 from .safe_pickle import UnsafePickleError, load_ndarray  # noqa: F401

@@ -161,6 +161,30 @@ def dft_plan_info(M: int) -> tuple:
     return int(n_pass.value), int(radix8.value), int(rpg.value)
 
 
+def _alloc_arrays(allocs, width):
+    """(n, start, M[, mod]) of a list of allocations as contiguous int32 arrays"""
+    a = np.asarray(list(allocs), dtype=np.int64).reshape(-1, width) if len(allocs) else np.zeros((0, width), np.int64)
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError("allocation entries must fit int32")
+    return (int(a.shape[0]),) + tuple(np.ascontiguousarray(a[:, k], dtype=np.int32) for k in range(width))
+
+
+def alloc_layout(M, mod, n_seg: int, rows: int, bits_mode: int = BITS_NONE) -> dict:
+    """ofdm_alloc_layout: where the blocks of an allocation set lie in the allocation-major outputs of
+    RxEngine.dft_despread_alloc_frames.  M and mod are the sizes and bits per symbol of the allocations in list order.  Returns
+    dict(sym_off, llr_off, bits_off: int64 arrays; sym, llr, bits: the totals) in complex items, floats and bytes."""
+    M = np.ascontiguousarray(M, dtype=np.int32)
+    mod = np.ascontiguousarray(mod, dtype=np.int32)
+    if M.ndim != 1 or M.shape != mod.shape:
+        raise ValueError("M and mod must be lists of one length")
+    n = int(M.size)
+    so, lo, bo = (np.zeros(max(n, 1), np.int64) for _ in range(3))
+    tot = np.zeros(3, np.int64)
+    check(_lib.load().ofdm_alloc_layout(n, ptr(M) if n else None, ptr(mod) if n else None, int(n_seg), int(rows), int(bits_mode),
+                                        ptr(so), ptr(lo), ptr(bo), ptr(tot)))
+    return dict(sym_off=so[:n], llr_off=lo[:n], bits_off=bo[:n], sym=int(tot[0]), llr=int(tot[1]), bits=int(tot[2]))
+
+
 def crc_bits(kind: int) -> int:
     """ofdm_crc_bits: the parity bits L of a CRC kind (CRC24A, CRC24B: 24, CRC16: 16, CRC8: 8)."""
     return int(check(_lib.load().ofdm_crc_bits(int(kind))))
@@ -419,6 +443,37 @@ class RxEngine(_Handle):
         return int(check(self.lib.ofdm_rx_demod_frames_despread(self._h, ptr(d_iq), int(n_frames), int(frame_stride), int(frame_len),
                                                                 ptr(d_eq), ptr(d_tsr), int(noise_mode), float(noise_var),
                                                                 ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream))))
+
+    # ---- multi-user allocations of DFT-spread OFDM (include/ofdm_mi355x.h, "multi-user allocations of DFT-spread OFDM") ---------
+    def set_allocations(self, allocs):
+        """ofdm_rx_set_allocations: a list of (start, M, bits per symbol), at most 32, not overlapping; () clears the set."""
+        n, start, M, mod = _alloc_arrays([(a[0], a[1], _mod_bits(a[2])) for a in allocs], 3)
+        check(self.lib.ofdm_rx_set_allocations(self._h, n, ptr(start) if n else None, ptr(M) if n else None, ptr(mod) if n else None))
+
+    def reserve_despread_alloc(self, n_seg: int = 0):
+        """ofdm_rx_reserve_despread_alloc: the tables of n_seg segments for the set in force (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_despread_alloc(self._h, int(n_seg)))
+
+    def dft_despread_alloc_frames(self, d_sym, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, d_sym_out=None, d_llr=None,
+                                  d_bits=None, bits_mode=BITS_NONE, d_beta=None, d_weight=None, noise_mode=_lib.DESPREAD_NOISE_RHO,
+                                  noise_var=0.0, d_sigma2=None, stream=None):
+        """ofdm_dft_despread_alloc_frames: every allocation of the set despread in one pass over rows of row_len symbols.  The
+        outputs are allocation-major and dense (alloc_layout); beta and weight are [n_alloc][n_seg]."""
+        out = self._despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight)
+        check(self.lib.ofdm_dft_despread_alloc_frames(self._h, ptr(d_sym), int(n_seg), int(rows), int(row_len), int(seg_stride),
+                                                      ptr(d_csi), int(csi_stride), float(rho), int(noise_mode), float(noise_var),
+                                                      ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream)))
+
+    def demod_frames_despread_alloc(self, d_iq, n_frames, frame_stride, frame_len, d_eq, d_sym_out=None, d_llr=None, d_bits=None,
+                                    bits_mode=BITS_NONE, d_beta=None, d_weight=None, noise_mode=_lib.DESPREAD_NOISE_RHO,
+                                    noise_var=0.0, d_sigma2=None, d_tsr=None, stream=None) -> int:
+        """demod_frames, then csi_frames(CSI_ROWS_ALL) into the workspace and dft_despread_alloc_frames over d_eq with one segment
+        per frame (n_dsym rows of row_len = Kd symbols, the handle's rho).  Returns n_dsym."""
+        out = self._despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight)
+        return int(check(self.lib.ofdm_rx_demod_frames_despread_alloc(self._h, ptr(d_iq), int(n_frames), int(frame_stride),
+                                                                      int(frame_len), ptr(d_eq), ptr(d_tsr), int(noise_mode),
+                                                                      float(noise_var), ptr(d_sigma2), int(bits_mode), C.byref(out),
+                                                                      ptr(stream))))
 
     # ---- receive-diversity combining: B branches added with maximum-ratio weights, LLRs of the sum (include/ofdm_mi355x.h) ------
     @staticmethod
@@ -960,6 +1015,29 @@ class TxEngine(_Handle):
             frame_stride = int(n_sym) * (self.cfg.nfft + self.cfg.cp_len)
         return int(check(self.lib.ofdm_tx_modulate_frames_spread(self._h, ptr(d_bits), int(bits_mode), int(n_frames), int(n_sym),
                                                                  ptr(d_iq), int(frame_stride), ptr(stream))))
+
+    # ---- multi-user allocations of DFT-spread OFDM (include/ofdm_mi355x.h, "multi-user allocations of DFT-spread OFDM")
+    def set_allocations(self, allocs):
+        """ofdm_tx_set_allocations: a list of (start, M), at most 32, not overlapping; () clears the set."""
+        n, start, M = _alloc_arrays([(a[0], a[1]) for a in allocs], 2)
+        check(self.lib.ofdm_tx_set_allocations(self._h, n, ptr(start) if n else None, ptr(M) if n else None))
+
+    def reserve_spread_alloc(self, n_rows: int = 0):
+        """ofdm_tx_reserve_spread_alloc: the workspace of modulate_frames_alloc for n_rows data symbols (before a graph capture)."""
+        check(self.lib.ofdm_tx_reserve_spread_alloc(self._h, int(n_rows)))
+
+    def dft_spread_alloc(self, d_sym, n_rows, row_len, d_out, stream=None):
+        """ofdm_tx_dft_spread_alloc: every allocation of every row replaced by its orthonormal DFT, every other entry by 0; d_out
+        may be d_sym."""
+        check(self.lib.ofdm_tx_dft_spread_alloc(self._h, ptr(d_sym), int(n_rows), int(row_len), ptr(d_out), ptr(stream)))
+
+    def modulate_frames_alloc(self, d_bits, n_frames, n_sym, d_iq, frame_stride=None, bits_mode=BITS_UNPACKED, stream=None) -> int:
+        """ofdm_tx_modulate_frames_alloc: modulate_frames_spread with dft_spread_alloc (row_len = num_data_bins) in place of the
+        single transform.  Returns the symbols written."""
+        if frame_stride is None:
+            frame_stride = int(n_sym) * (self.cfg.nfft + self.cfg.cp_len)
+        return int(check(self.lib.ofdm_tx_modulate_frames_alloc(self._h, ptr(d_bits), int(bits_mode), int(n_frames), int(n_sym),
+                                                                ptr(d_iq), int(frame_stride), ptr(stream))))
 
     def sync_symbol(self) -> np.ndarray:
         c = self.cfg
