@@ -101,7 +101,11 @@ int ofdm_rx_get_state(ofdm_rx* h, int32_t row, float* h_chan_freq, float* h_chan
  * work() buffer processed with FRESH-instance semantics (own sync search from P=0, own channel
  * estimate; :143-248).  Frame f occupies d_iq[f*frame_stride .. +frame_len) (complex64 items).
  * n_pat = floor(floor(frame_len/L)/(S+D)) patterns are demodulated; outputs per frame:
- *   d_eq   [n_pat*D][Kd] complex64 equalised symbols (rows 3,7,.. of the reference already dropped), may be NULL
+ *   d_eq   [n_pat*D][Kd] complex64 equalised symbols, may be NULL: row p*D + n (p < n_pat, n < D) is the reference's
+ *          est_data_freq[p*(S+D) + n], i.e. the data rows of every pattern in order with the rows in between left out.  Pattern p
+ *          is read at the reference's pointer ptr_p = t0 + S*L*(p*(S+D) + 1) (:222, t0 = time_synch_ref[0]) and guarded once by
+ *          ptr_p + nfft - 1 <= frame_len (:223, else D rows of zeros); for S > 1 that pointer meets the pattern's data symbols at
+ *          p = 0 only, and the batch path restates it as it is.
  *   d_bits hard bits of those symbols: packed MSB-first [n_pat*D*Kd*bps/8] bytes or unpacked [..*bps] bytes, may be NULL
  *   d_tsr  [4] int32: time_synch_ref[0..2], detected flag, may be NULL
  * Asynchronous on `stream`.  Returns n_pat*D (data symbols per frame) or a negative ofdm_status. */
