@@ -617,6 +617,59 @@ int ofdm_tx_reserve_spread_alloc(struct ofdm_tx* h, int64_t n_rows);
 int64_t ofdm_tx_modulate_frames_alloc(struct ofdm_tx* h, const uint8_t* d_bits, int32_t bits_mode, int64_t n_frames, int32_t n_sym,
                                       float* d_iq, int64_t frame_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------ receive diversity for multi-user allocations of DFT-spread OFDM
+ * An extension the reference does not have: the base station's receiver, with B antennas and several users in every symbol.  It
+ * is "receive diversity for DFT-spread OFDM" above with the allocation set of "multi-user allocations of DFT-spread OFDM" in
+ * place of the single M.  (Combining first with ofdm_combine_csi_frames and despreading with ofdm_dft_despread_alloc_frames gives
+ * wrong weights: beta and the noise behind the transform must come from the COMBINED channel of each user's own columns.)  This
+ * text is the definition; tests/mrc_despread_alloc_ref.py restates it in NumPy (a loop over the allocations around
+ * tests/mrc_despread_ref.py).
+ *
+ * The contract in one sentence: for every allocation u of the handle's set, block u of every output -- sym, llr, bits, beta,
+ * weight and comb -- holds bit for bit what ofdm_combine_despread_frames writes for M = M_u and modulation = mod_u when given a
+ * dense copy of columns start_u .. start_u+M_u-1 of every row of every branch, the same columns of every unit's d_csi row, the
+ * same rho and the same noise.  Steps 1-7 of the receive-diversity-for-DFT-spread contract apply per allocation, word for word.
+ * Entries outside every allocation are never read for data.
+ *
+ * Inputs, branch-major as ofdm_combine_despread_frames: unit g = b*n_seg + s is `rows` rows of row_len complex64 at
+ * d_sym + g*seg_stride (complex items), with row_len channel powers (float32) at d_csi + g*csi_stride.  d_csi is required: the
+ * combiner has no meaning without it.  Outputs: sym, comb, llr and bits are allocation-major and dense at the offsets
+ * ofdm_alloc_layout returns (comb uses the sym offsets); beta and weight are per row, [n_alloc][n_seg][rows]: row r of segment s
+ * of allocation u at (u*n_seg + s)*rows + r.
+ * Noise: OFDM_MRC_NOISE_GIVEN (HOST array h_noise_var[n_branch]) and OFDM_MRC_NOISE_SEG (DEVICE doubles d_sigma2[n_branch*n_seg]).
+ * A unit's variance is shared by all its allocations: it is the receiver's noise, not a user's.  OFDM_MRC_NOISE_EST is refused.
+ * Position independence: a user's bits depend on (B, M_u) and its own columns alone.  They are the same in any batch, at any
+ * start, at either alignment of every branch (alignment is decided per row and per branch; it alternates between rows where
+ * row_len or start is odd and between branches where n_seg*seg_stride is odd), with any other users in the set, and on every
+ * call. */
+/* Sizes the {c, t} table of the stage for n_branch*n_seg*row_len entries and the |H|^2 rows of
+ * ofdm_rx_demod_frames_mrc_despread_alloc for n_branch*n_seg*num_data_bins floats, and loads the kernels.  Needs no set: the
+ * workspace does not depend on it, and the set is not copied into the plan cache.  Grows, never shrinks; synchronises the device.
+ * After it the stage enqueues without host synchronisation or allocation and can be captured and replayed; inside a capture a
+ * call that needs more is refused before anything is enqueued. */
+int ofdm_rx_reserve_mrc_despread_alloc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t row_len);
+/* The stage on any device buffer, over the set ofdm_rx_set_allocations installed.  Asynchronous on `stream`: the combiner's table
+ * over the whole rows, then at most one launch per (M <= 2048 or not, modulation) pair present in the set -- one per size class
+ * when neither llr nor bits is wanted; the count does not depend on the number of users or branches.  n_seg == 0 or rows == 0
+ * is a no-op.  Refusals are OFDM_ERR_INVALID with the reason in ofdm_last_error(), before anything is enqueued or any output
+ * touched: everything ofdm_combine_despread_frames refuses, per allocation; everything ofdm_dft_despread_alloc_frames refuses for
+ * the same argument (no set, row_len < max(start + M), seg_stride < rows*row_len, csi_stride < row_len, packed bits with an
+ * allocation whose row bits do not fill bytes); index ranges (n_branch*n_seg > 2^31, more than 2^31 - 1 workgroups);
+ * out->sym or out->comb equal to d_sym (the layouts differ); d_csi NULL; growth inside a stream capture. */
+int ofdm_combine_despread_alloc_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len,
+                                       int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, int32_t noise_mode,
+                                       const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                       const ofdm_mrc_despread_out* out, void* stream);
+/* d_iq in the layout of ofdm_rx_demod_frames_mrc (frame f of branch b at index b*n_frames + f).  Runs ofdm_rx_demod_frames over
+ * the n_branch*n_frames frames (d_eq required), then ofdm_rx_csi_frames(OFDM_CSI_ROWS_ALL) into the workspace, then the stage with
+ * row_len = num_data_bins, one segment per frame and rho from the handle.  Follows ofdm_rx_set_chan_window and
+ * ofdm_rx_set_chan_average like every ofdm_rx_demod_frames_* call.  d_sigma2 (OFDM_MRC_NOISE_SEG) is [n_branch*n_frames].  Every
+ * check is made before anything is enqueued.  Returns n_dsym or a negative status. */
+int64_t ofdm_rx_demod_frames_mrc_despread_alloc(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames,
+                                                int64_t frame_stride, int64_t frame_len, float* d_eq, int32_t* d_tsr,
+                                                int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
+                                                int32_t bits_mode, const ofdm_mrc_despread_out* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------ delay-window channel-estimate denoising
  * An extension the reference does not have.  The batch receiver's channel estimate is the least-squares (LS) estimate of ONE
  * Zadoff-Chu preamble symbol: as noisy as one received symbol.  A channel is shorter than the cyclic prefix, so nearly all of that

@@ -3,7 +3,8 @@
 // OFDM"), and the stage that combines B receive branches before it despreads, with its composite call
 // ("receive diversity for DFT-spread OFDM"): it lives here for the plan cache.  Last, the allocation sets of
 // both handles and the calls that walk them ("multi-user allocations of DFT-spread OFDM"): they share the
-// argument checks of the despreading stage.
+// argument checks of the despreading stage; and the stage that combines B branches per allocation of that set ("receive diversity
+// for multi-user allocations of DFT-spread OFDM").
 #include "capi_internal.hpp"
 
 void dft_plans_free(DftPlanCache& c) {
@@ -795,6 +796,168 @@ int64_t ofdm_tx_modulate_frames_alloc(ofdm_tx* h, const uint8_t* d_bits, int32_t
     if (rc == OFDM_OK) rc = ofdm_tx_ifft_cp(h, grid, rows, 1, 1, time, stream);
     if (rc != OFDM_OK) return rc;
     return ofdm_tx_mux(h, time, rows, d_iq, stream);
+}
+
+}  // extern "C"
+
+// ---- receive diversity for multi-user allocations of DFT-spread OFDM (include/ofdm_mi355x.h, "receive diversity for multi-user
+// allocations of DFT-spread OFDM"): the stage of 9.2.16 over the allocation set of 9.2.17.  The set is the
+// handle's (ofdm_rx_set_allocations); the workspace is a group of its own and does not depend on the set.
+namespace {
+
+// what the arguments and the set decide (no device access); "" = fine.  First what the arguments alone decide, then the set.
+const char* mrc_despread_alloc_bad_args(const DftAllocSet& A, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows,
+                                        int64_t row_len, int64_t seg_stride, int64_t csi_stride, float rho, int32_t noise_mode,
+                                        const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                        const ofdm_mrc_despread_out* out) {
+    if (noise_mode == OFDM_MRC_NOISE_EST)
+        return "OFDM_MRC_NOISE_EST is refused (a spread signal has no constellation points per bin): pass OFDM_MRC_NOISE_GIVEN or "
+               "OFDM_MRC_NOISE_SEG";
+    // the modulations are the set's: 2 stands in where the combiner's checks ask for one
+    const char* bad = mrc_bad_args(n_branch, n_seg, rows, row_len, seg_stride, csi_stride, rho, 2, noise_mode, h_noise_var, d_sigma2, false);
+    if (*bad) return bad;
+    if (!mrc_despread_wanted(out)) return "out is NULL or holds no pointer";
+    if (out->bits && !bits_mode_ok(bits_mode)) return "bits wanted: bits_mode must be OFDM_BITS_PACKED or OFDM_BITS_UNPACKED";
+    if (d_sym && (out->sym == d_sym || out->comb == d_sym)) return "out->sym or out->comb == d_sym is refused: the layouts differ";
+    // every allocation of any set takes at least one workgroup per segment: this much of the grid's limit the arguments decide
+    if (rows > 0 && n_seg > DFT_MAX_GROUPS) return "index range exceeded (more than 2^31 - 1 workgroups)";
+    if (A.n == 0) return "no allocation set (ofdm_rx_set_allocations)";
+    if (row_len < A.max_end) return "row_len < max(start + M) of the allocation set";
+    int64_t groups = 0;
+    for (int u = 0; u < A.n; ++u) {
+        const DftPlan& pl = A.h[u].pl;
+        if (out->bits && bits_mode == OFDM_BITS_PACKED && (int64_t(pl.M) * A.h[u].mod) % 8 != 0)
+            return "packed bits need M * bits per symbol % 8 == 0 of every allocation";
+        if (!dft_rows_in_range(pl, rows, n_seg)) return "index range exceeded (more than 2^31 - 1 workgroups)";
+        groups += n_seg * ((rows + pl.rows_per_group - 1) / pl.rows_per_group);     // each term fits (checked above)
+        if (groups > DFT_MAX_GROUPS) return "index range exceeded (more than 2^31 - 1 workgroups)";
+    }
+    return "";
+}
+int mrc_despread_alloc_ensure(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t row_len, bool composite, hipStream_t s,
+                              const char* who) {
+    const int64_t units = n_branch * n_seg;
+    if (units * row_len <= h->cap_ma_tab && (!composite || units * h->dev.Kd <= h->cap_ma_a)) return OFDM_OK;
+    const int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_mrc_despread_alloc");
+    return rc != OFDM_OK ? rc : ofdm_rx_reserve_mrc_despread_alloc(h, n_branch, n_seg, row_len);
+}
+// d_sigma2 == null: the host array (OFDM_MRC_NOISE_GIVEN)
+int mrc_despread_alloc_launch(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len,
+                              int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, const double* h_noise_var,
+                              const double* d_sigma2, int32_t bits_mode, const ofdm_mrc_despread_out* out, hipStream_t s) {
+    MrcArgs t{};                                            // the table over the whole rows: gaps are computed and never read
+    t.n_branch = n_branch;
+    t.n_seg = n_seg;
+    t.rows = rows;
+    t.seg_stride = seg_stride;
+    t.row_len = int(row_len);
+    t.seg_len = rows * row_len;
+    t.csi = d_csi;
+    t.csi_stride = csi_stride;
+    t.rho = rho;
+    t.mod = 2;                                              // not read by the table
+    t.sigma2 = d_sigma2;
+    for (int b = 0; b < MRC_MAX_BRANCHES; ++b) t.noise_var[b] = (!d_sigma2 && b < n_branch) ? h_noise_var[b] : 0.0;
+    t.tab = h->ma_tab;
+    HIP_TRY(launch_mrc_table(t, s));
+    MrcDespreadAllocArgs a{};
+    a.set = h->alloc.d_set;
+    a.n_alloc = h->alloc.n;
+    a.sym = reinterpret_cast<const cf*>(d_sym);
+    a.n_branch = n_branch;
+    a.n_seg = n_seg;
+    a.rows = rows;
+    a.row_len = row_len;
+    a.seg_stride = seg_stride;
+    a.tab = h->ma_tab;
+    a.bits_mode = bits_mode;
+    a.osym = reinterpret_cast<cf*>(out->sym);
+    a.llr = out->llr;
+    a.bits = out->bits;
+    a.beta = out->beta;
+    a.weight = out->weight;
+    a.comb = reinterpret_cast<cf*>(out->comb);
+    HIP_TRY(launch_mrc_despread_alloc(a, h->alloc.h, s));
+    return OFDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ofdm_rx_reserve_mrc_despread_alloc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t row_len) {
+    const char* who = "ofdm_rx_reserve_mrc_despread_alloc";
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES) return fail(OFDM_ERR_INVALID, "%s: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES", who);
+    if (n_seg < 0 || row_len < 0) return fail(OFDM_ERR_INVALID, "%s: negative count", who);
+    if (n_seg > SOFT_MAX_N / n_branch || row_len > SOFT_MAX_ROW) return fail(OFDM_ERR_INVALID, "%s: batch too large", who);
+    const int64_t units = n_branch * n_seg;
+    if (units > 0 && (row_len > SOFT_MAX_LEN / units || h->dev.Kd > SOFT_MAX_LEN / units))
+        return fail(OFDM_ERR_INVALID, "%s: batch too large", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    HIP_TRY(mrc_despread_alloc_prepare());
+    if (units * row_len > h->cap_ma_tab) {
+        const int rc = regrow(h, {{&h->cap_ma_tab, units * row_len}}, ws_buf(&h->ma_tab, size_t(units * row_len)));
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t floats = units * h->dev.Kd;
+    if (floats <= h->cap_ma_a) return OFDM_OK;
+    return regrow(h, {{&h->cap_ma_a, floats}}, ws_buf(&h->ma_a, size_t(floats)));
+}
+
+int ofdm_combine_despread_alloc_frames(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len,
+                                       int64_t seg_stride, const float* d_csi, int64_t csi_stride, float rho, int32_t noise_mode,
+                                       const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                       const ofdm_mrc_despread_out* out, void* stream) {
+    const char* who = "ofdm_combine_despread_alloc_frames";
+    if (!h) return fail(OFDM_ERR_INVALID, "%s: null handle", who);
+    if (!d_csi) return fail(OFDM_ERR_INVALID, "%s: d_csi is required (the combiner has no meaning without it)", who);
+    const char* bad = mrc_despread_alloc_bad_args(h->alloc, d_sym, n_branch, n_seg, rows, row_len, seg_stride, csi_stride, rho, noise_mode,
+                                                  h_noise_var, d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    if (n_seg == 0 || rows == 0) return OFDM_OK;
+    if (!d_sym) return fail(OFDM_ERR_INVALID, "%s: null d_sym", who);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = pick_stream(h, stream);
+    const int rc = mrc_despread_alloc_ensure(h, n_branch, n_seg, row_len, false, s, who);
+    if (rc != OFDM_OK) return rc;
+    return mrc_despread_alloc_launch(h, d_sym, n_branch, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, h_noise_var,
+                                     noise_mode == OFDM_MRC_NOISE_SEG ? d_sigma2 : nullptr, bits_mode, out, s);
+}
+
+int64_t ofdm_rx_demod_frames_mrc_despread_alloc(ofdm_rx* h, const float* d_iq, int32_t n_branch, int64_t n_frames, int64_t frame_stride,
+                                                int64_t frame_len, float* d_eq, int32_t* d_tsr, int32_t noise_mode,
+                                                const double* h_noise_var, const double* d_sigma2, int32_t bits_mode,
+                                                const ofdm_mrc_despread_out* out, void* stream) {
+    const char* who = "ofdm_rx_demod_frames_mrc_despread_alloc";
+    const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, who);
+    if (open != OFDM_OK) return open;
+    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES)
+        return fail(OFDM_ERR_INVALID, "%s: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES", who);
+    if (n_frames > SOFT_MAX_N / n_branch) return fail(OFDM_ERR_INVALID, "%s: batch too large (n_branch * n_frames > 2^31)", who);
+    if (!d_eq) return fail(OFDM_ERR_INVALID, "%s: the stage needs d_eq (it reads it)", who);
+    const RxDev& d = h->dev;
+    const int64_t units = n_branch * n_frames;
+    const int64_t n_dsym = frame_data_symbols(d, frame_len);
+    // the checks of the stages, made here first so that a bad call enqueues nothing
+    const char* bad = demod_bad_args(d, units, n_dsym, nullptr, OFDM_BITS_NONE);
+    if (!*bad)
+        bad = mrc_despread_alloc_bad_args(h->alloc, d_eq, n_branch, n_frames, n_dsym, d.Kd, n_dsym * d.Kd, d.Kd, d.inv_snr_data, noise_mode,
+                                          h_noise_var, d_sigma2, bits_mode, out);
+    if (*bad) return fail(OFDM_ERR_INVALID, "%s: %s", who, bad);
+    hipStream_t s = pick_stream(h, stream);
+    const bool run = n_frames > 0 && n_dsym > 0;
+    if (run) {                                              // grow first: nothing is enqueued unless the whole call can run
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        const int rc = mrc_despread_alloc_ensure(h, n_branch, n_frames, d.Kd, true, s, who);
+        if (rc != OFDM_OK) return rc;
+    }
+    const int64_t r = ofdm_rx_demod_frames(h, d_iq, units, frame_stride, frame_len, d_eq, nullptr, OFDM_BITS_NONE, d_tsr, stream);
+    if (r < 0 || !run) return r;
+    HIP_TRY(launch_csi_frames(h->f_H, d.nfft, d.Kd, nullptr, d.Kd, units, h->ma_a, d.Kd, s));
+    const int rc = mrc_despread_alloc_launch(h, d_eq, n_branch, n_frames, n_dsym, d.Kd, n_dsym * d.Kd, h->ma_a, d.Kd, d.inv_snr_data,
+                                             h_noise_var, noise_mode == OFDM_MRC_NOISE_SEG ? d_sigma2 : nullptr, bits_mode, out, s);
+    return rc != OFDM_OK ? rc : r;
 }
 
 }  // extern "C"

@@ -173,6 +173,11 @@ struct ofdm_rx {
     int64_t cap_da_tab = 0;              // entries
     float* da_a = nullptr;               // [n_seg][Kd] |H|^2 rows of ofdm_rx_demod_frames_despread_alloc
     int64_t cap_da_seg = 0;
+    // ---- receive diversity for multi-user allocations (ofdm_rx_reserve_mrc_despread_alloc); the set is the one above
+    float2* ma_tab = nullptr;            // [n_branch*n_seg][row_len] {c, t} over the whole rows (mrc_table_kernel)
+    int64_t cap_ma_tab = 0;              // entries
+    float* ma_a = nullptr;               // [n_branch*n_frames][Kd] |H|^2 rows of ofdm_rx_demod_frames_mrc_despread_alloc
+    int64_t cap_ma_a = 0;                // floats
     // ---- turbo decoder workspace (ofdm_rx_reserve_turbo): extrinsic values [n_blocks][K], then the forward checkpoints;
     // ofdm_rx_reserve_turbo_es: a second [n_blocks][K] array (post) between the two.  One buffer, laid out per call.
     float* t_ws = nullptr;

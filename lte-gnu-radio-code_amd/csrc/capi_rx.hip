@@ -21,7 +21,7 @@ int ofdm_rx_destroy(ofdm_rx* h) {
              &h->k_H, &h->k_flag, &h->k_nb, &h->k_rtsr, &h->k_eq, &h->ds_tab, &h->ds_a, &h->md_tab, &h->md_a);
     dft_plans_free(h->dft);
     dft_alloc_free(h->alloc);
-    free_dev(&h->da_tab, &h->da_a);
+    free_dev(&h->da_tab, &h->da_a, &h->ma_tab, &h->ma_a);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->ev_up) (void)hipEventDestroy(h->ev_up);

@@ -299,6 +299,28 @@ struct DftAllocRowsArgs {
 hipError_t launch_dft_alloc_rows(DftAllocRowsArgs a, const DftAllocDesc* h_set, int n_alloc, hipStream_t s);
 hipError_t dft_alloc_prepare();          // loads the kernels (before a stream capture)
 
+// ---- receive diversity for multi-user allocations of DFT-spread OFDM (mrc_despread_alloc.hip; contract: include/ofdm_mi355x.h,
+// "receive diversity for multi-user allocations of DFT-spread OFDM").  launch_mrc_table over the whole rows
+// (row_len entries per unit), then one launch per class of the set; a workgroup serves (allocation, segment, group of rows).
+struct MrcDespreadAllocArgs {
+    const DftAllocDesc* set;
+    int n_alloc;
+    const cf* sym;           // unit g = b*n_seg + s: rows rows of row_len at sym + g*seg_stride
+    int n_branch;
+    int64_t n_seg, rows, row_len, seg_stride;     // complex items
+    const float2* tab;       // [n_branch*n_seg][row_len] {c, t} of launch_mrc_table
+    int bits_mode;           // ofdm_bits_mode
+    cf* osym;                // allocation-major dense blocks, or null
+    float* llr;
+    uint8_t* bits;
+    float* beta;             // [n_alloc][n_seg][rows], or null
+    float* weight;
+    cf* comb;                // the combined symbols before the transform, laid out as osym, or null
+};
+// h_set: the host copy of the table (plans, modulations).  The caller has checked the arguments and every grid, and run the table.
+hipError_t launch_mrc_despread_alloc(const MrcDespreadAllocArgs& a, const DftAllocDesc* h_set, hipStream_t s);
+hipError_t mrc_despread_alloc_prepare(); // loads the kernels of both launches (before a stream capture)
+
 // ---- pilot-aided phase tracking (ofdm_pilot_track_frames): rows of K equalised symbols in binsP(K) list order -> rows of
 // Kd = K - n_pilots de-rotated data symbols.  A row is owned by a group of 2^g_log2 lanes of one wave (one lane per PAIR of
 // consecutive outputs and pass); a group walks rows_per_group consecutive rows, so that a workgroup's share is sized in bytes.

@@ -265,6 +265,13 @@ PROTOTYPES = {
     "ofdm_tx_reserve_spread_alloc": (C.c_int, [C.c_void_p, C.c_int64]),
     "ofdm_tx_modulate_frames_alloc": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
                                                   C.c_void_p]),
+    "ofdm_rx_reserve_mrc_despread_alloc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64]),
+    "ofdm_combine_despread_alloc_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                                     C.c_void_p, C.c_int64, C.c_float, C.c_int32, C.POINTER(C.c_double),
+                                                     C.c_void_p, C.c_int32, C.POINTER(MrcDespreadOut), C.c_void_p]),
+    "ofdm_rx_demod_frames_mrc_despread_alloc": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                                            C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                                                            C.c_int32, C.POINTER(MrcDespreadOut), C.c_void_p]),
     "ofdm_tbcc_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
     "ofdm_tx_tbcc_encode_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_int32, C.c_int64, C.c_void_p]),

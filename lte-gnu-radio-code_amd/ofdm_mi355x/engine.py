@@ -568,6 +568,47 @@ class RxEngine(_Handle):
                                                                     MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2),
                                                                     int(bits_mode), C.byref(out), ptr(stream))))
 
+    # ---- receive diversity for multi-user allocations of DFT-spread OFDM (include/ofdm_mi355x.h) ---------------------------------
+    def reserve_mrc_despread_alloc(self, n_branch: int, n_seg: int = 0, row_len: int = 0):
+        """ofdm_rx_reserve_mrc_despread_alloc: the table of n_branch*n_seg units of row_len entries and the |H|^2 rows of
+        demod_frames_mrc_despread_alloc for as many frames (before a graph capture)."""
+        check(self.lib.ofdm_rx_reserve_mrc_despread_alloc(self._h, int(n_branch), int(n_seg), int(row_len)))
+
+    def combine_despread_alloc_frames(self, d_sym, n_branch, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, noise_var=None,
+                                      d_sigma2=None, d_sym_out=None, d_llr=None, d_bits=None, bits_mode=BITS_NONE, d_beta=None,
+                                      d_weight=None, d_comb=None, stream=None):
+        """ofdm_combine_despread_alloc_frames: combine_despread_frames for every allocation of the set (set_allocations) in one
+        pass over rows of row_len symbols: unit g = b*n_seg + s is `rows` rows at d_sym + g*seg_stride with the channel powers
+        d_csi[g*csi_stride + k].  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device, [n_branch*n_seg] float64).
+        sym, comb, llr and bits are allocation-major and dense (alloc_layout; comb at the sym offsets); beta and weight are
+        [n_alloc][n_seg][rows]."""
+        if (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("combine_despread_alloc_frames: give exactly one of noise_var and d_sigma2")
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
+        check(self.lib.ofdm_combine_despread_alloc_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(row_len),
+                                                          int(seg_stride), ptr(d_csi), int(csi_stride), float(rho),
+                                                          MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2),
+                                                          int(bits_mode), C.byref(out), ptr(stream)))
+
+    def demod_frames_mrc_despread_alloc(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_sigma2=None,
+                                        d_sym_out=None, d_llr=None, d_bits=None, bits_mode=BITS_NONE, d_beta=None, d_weight=None,
+                                        d_comb=None, d_tsr=None, stream=None) -> int:
+        """demod_frames over the n_branch*n_frames frames of d_iq (frame f of branch b at index b*n_frames + f), then
+        csi_frames(CSI_ROWS_ALL) into the workspace and combine_despread_alloc_frames over d_eq with one segment per frame (n_dsym
+        rows of row_len = Kd symbols, the handle's rho).  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device,
+        [n_branch*n_frames] float64).  Returns n_dsym."""
+        if (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("demod_frames_mrc_despread_alloc: give exactly one of noise_var and d_sigma2")
+        given = noise_var is not None
+        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
+        return int(check(self.lib.ofdm_rx_demod_frames_mrc_despread_alloc(self._h, ptr(d_iq), int(n_branch), int(n_frames),
+                                                                          int(frame_stride), int(frame_len), ptr(d_eq), ptr(d_tsr),
+                                                                          MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv,
+                                                                          ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream))))
+
     # ---- delay-window denoising of the LS channel estimate (include/ofdm_mi355x.h) ----------------------------------------------
     def set_chan_window(self, pre: int, post: int):
         """ofdm_rx_set_chan_window: while (pre, post) != (0, 0), demod_frames -- and every demod_frames_* call -- refines its
