@@ -2,8 +2,8 @@
 // contiguous run of entries, its own transform size and (receiver) its own modulation, gain and weight.  Definition:
 // include/ofdm_mi355x.h, "multi-user allocations of DFT-spread OFDM"; DESIGN.md 9.2.17.  No reference code.
 //
-//   despread_alloc_table_kernel               one workgroup of 256 per (allocation, segment): the sums of despread_table_kernel
-//                                             (dft_spread.hip) over the allocation's entries, same lane order, same block_sum
+//   despread_alloc_table_kernel               one workgroup of 256 per (allocation, segment): segment_weights (dft_rows_device.hpp),
+//                                             which despread_table_kernel (dft_spread.hip) calls too, over the allocation's entries
 //   despread_alloc_rows_kernel<MOD, MORE, CAP> one workgroup per (allocation, segment, group of rows_per_group(M_u) rows): strided
 //                                             staging, dft_rows_in_lds, despread_epilogue (dft_rows_device.hpp)
 //   dft_alloc_rows_kernel<CAP>                the transmitter: every allocation of a row replaced by its DFT, the gaps by +0
@@ -13,61 +13,25 @@
 // workgroup finds its allocation from blockIdx.x by a wave-uniform walk over the class's prefix sums (<= 32 entries, in the
 // kernel arguments: they depend on the call's rows and n_seg, the set's table on the device does not).  The plan and the
 // twiddles are read from the set's table.  An element's bits depend on (M_u, the row's entries) alone: they are those of the
-// single-M kernels on a dense copy of the allocation's columns.
+// single-M kernels on a dense copy of the allocation's columns -- segment_weights, dft_rows_in_lds and despread_epilogue are the
+// functions those kernels call; what differs is the addressing.  The classes and the lookup are in dft_rows_launch.hpp.
 #include "dft_rows_device.hpp"
+#include "dft_rows_launch.hpp"
 
 namespace ofdm {
-
-namespace {
-
-// the class's allocation of workgroup b: k with end[k-1] <= b < end[k]; uniform over the workgroup
-__device__ __forceinline__ int alloc_of(const DftAllocClass& c, unsigned b, unsigned& first) {
-    int k = 0;
-    first = 0;
-    while (k < c.n - 1 && b >= c.end[k]) first = c.end[k++];
-    return k;
-}
-
-}  // namespace
 
 __global__ void __launch_bounds__(256) despread_alloc_table_kernel(DespreadAllocArgs a, const DftAllocDesc* __restrict__ set) {
     __shared__ double sh0[4], sh1[4];
     const int64_t u = int64_t(blockIdx.x) / a.n_seg, s = int64_t(blockIdx.x) - u * a.n_seg;
-    const int M = set[u].pl.M;
-    float inv = 1.f, wgt = 1.f, bet = 1.f;
+    float4 t{1.f, 1.f, 1.f, 1.f};
     if (a.csi) {
-        const float* csi = a.csi + s * a.csi_stride + set[u].start;
-        const double rho = double(a.rho);
-        const double sigma2 = a.noise_mode == 0 ? rho : a.noise_mode == 1 ? a.noise_var : a.sigma2[s];
-        double sb = 0.0;
-        for (int k = threadIdx.x; k < M; k += 256) {
-            const float av = csi[k];
-            if (soft_finite(av) && av > 0.f) sb += double(av) / (double(av) + rho);
-        }
-        const double beta = block_sum(sb, sh0) / double(M);
-        double sv = 0.0;
-        for (int k = threadIdx.x; k < M; k += 256) {
-            const float av = csi[k];
-            const bool ok = soft_finite(av) && av > 0.f;
-            const double ad = double(av), den = ad + rho;
-            const double b = ok ? ad / den : 0.0;
-            double t = (b - beta) * (b - beta);
-            if (ok) t += sigma2 * ad / (den * den);
-            sv += t;
-        }
-        const double nu = block_sum(sv, sh1) / double(M);
-        const double w = beta * beta / nu;
-        auto good = [](double x) { return fabs(x) < __builtin_inf() && x > 0.0; };
-        const float inv_f = float(1.0 / beta), w_f = float(w), b_f = float(beta);
-        const bool usable = good(beta) && good(nu) && good(w) && soft_finite(inv_f) && soft_finite(w_f);
-        inv = usable ? inv_f : 0.f;
-        wgt = usable ? w_f : 0.f;
-        bet = usable ? b_f : 0.f;
+        const double sigma2 = a.noise_mode == 0 ? double(a.rho) : a.noise_mode == 1 ? a.noise_var : a.sigma2[s];
+        t = segment_weights(a.csi + s * a.csi_stride + set[u].start, set[u].pl.M, double(a.rho), sigma2, sh0, sh1);
     }
     if (threadIdx.x == 0) {
-        a.tab[blockIdx.x] = float4{inv, wgt, bet, inv != 0.f ? 1.f : 0.f};
-        if (a.beta) a.beta[blockIdx.x] = bet;
-        if (a.weight) a.weight[blockIdx.x] = wgt;
+        a.tab[blockIdx.x] = t;
+        if (a.beta) a.beta[blockIdx.x] = t.z;
+        if (a.weight) a.weight[blockIdx.x] = t.y;
     }
 }
 
@@ -139,90 +103,38 @@ __global__ void __launch_bounds__(DFT_THREADS) dft_alloc_rows_kernel(DftAllocRow
     }
 }
 
-namespace {
-
-// the allocations of h_set[0 .. n) that `pick` accepts, with their workgroups: units (segments, or 1) times the groups of `rows`
-template <class Pick>
-DftAllocClass make_class(const DftAllocDesc* h_set, int n, int64_t units, int64_t rows, Pick pick) {
-    DftAllocClass c{};
-    uint64_t end = 0;
-    for (int u = 0; u < n; ++u) {
-        if (!pick(h_set[u])) continue;
-        const int rpg = h_set[u].pl.rows_per_group;
-        end += uint64_t(units) * uint64_t((rows + rpg - 1) / rpg);
-        c.idx[c.n] = uint8_t(u);
-        c.end[c.n++] = unsigned(end);
-    }
-    return c;
-}
-bool cap_small(const DftAllocDesc& d) { return d.pl.M <= DFT_SMALL_M; }
-
-template <int CAP>
-hipError_t launch_rows_class(const DespreadAllocArgs& a, const DftAllocClass& c, int mod, bool more, hipStream_t s) {
-    const dim3 g(c.end[c.n - 1]), b(DFT_THREADS);
-    if (!more) {
-        hipLaunchKernelGGL((despread_alloc_rows_kernel<2, false, CAP>), g, b, 0, s, a, c, a.set);
-    } else {
-        switch (mod) {
-            case 2: hipLaunchKernelGGL((despread_alloc_rows_kernel<2, true, CAP>), g, b, 0, s, a, c, a.set); break;
-            case 4: hipLaunchKernelGGL((despread_alloc_rows_kernel<4, true, CAP>), g, b, 0, s, a, c, a.set); break;
-            case 6: hipLaunchKernelGGL((despread_alloc_rows_kernel<6, true, CAP>), g, b, 0, s, a, c, a.set); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
-}
-
-}  // namespace
-
 hipError_t launch_despread_alloc(const DespreadAllocArgs& a, const DftAllocDesc* h_set, hipStream_t s) {
     if (a.n_seg <= 0 || a.rows <= 0 || a.n_alloc <= 0) return hipSuccess;
     hipLaunchKernelGGL(despread_alloc_table_kernel, dim3(unsigned(a.n_alloc * a.n_seg)), dim3(256), 0, s, a, a.set);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess || (!a.osym && !a.llr && !a.bits)) return e;
     const bool more = a.llr || a.bits;
-    for (int small = 1; small >= 0; --small) {
-        for (int mod = 2; mod <= (more ? 6 : 2); mod += 2) {
-            const DftAllocClass c = make_class(h_set, a.n_alloc, a.n_seg, a.rows, [&](const DftAllocDesc& d) {
-                return cap_small(d) == bool(small) && (!more || d.mod == mod);
-            });
-            if (c.n == 0) continue;
-            e = small ? launch_rows_class<DFT_SMALL_M>(a, c, mod, more, s) : launch_rows_class<DFT_MAX_M>(a, c, mod, more, s);
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
+    return for_each_alloc_class(h_set, a.n_alloc, a.n_seg, a.rows, more, [&](const DftAllocClass& c, bool small, int mod) {
+        return with_row_instance(small, more, mod, [&](auto I) {
+            hipLaunchKernelGGL((despread_alloc_rows_kernel<I.mod, I.more, I.cap>), dim3(c.end[c.n - 1]), dim3(DFT_THREADS), 0, s, a, c, a.set);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_dft_alloc_rows(DftAllocRowsArgs a, const DftAllocDesc* h_set, int n_alloc, hipStream_t s) {
     if (a.n_rows <= 0 || n_alloc <= 0) return hipSuccess;
-    unsigned zero = a.n_gap > 0 ? unsigned(std::min<int64_t>(a.n_rows, 1024)) : 0u;
-    for (int small = 1; small >= 0; --small) {
-        const DftAllocClass c = make_class(h_set, n_alloc, 1, a.n_rows, [&](const DftAllocDesc& d) { return cap_small(d) == bool(small); });
-        if (c.n == 0) continue;
-        a.zero_groups = zero;
-        const dim3 g(c.end[c.n - 1] + zero), b(DFT_THREADS);
+    a.zero_groups = a.n_gap > 0 ? unsigned(std::min<int64_t>(a.n_rows, 1024)) : 0u;
+    return for_each_alloc_class(h_set, n_alloc, 1, a.n_rows, false, [&](const DftAllocClass& c, bool small, int) {
+        const dim3 g(c.end[c.n - 1] + a.zero_groups), b(DFT_THREADS);
         if (small)
             hipLaunchKernelGGL((dft_alloc_rows_kernel<DFT_SMALL_M>), g, b, 0, s, a, c, a.set);
         else
             hipLaunchKernelGGL((dft_alloc_rows_kernel<DFT_MAX_M>), g, b, 0, s, a, c, a.set);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        zero = 0;                                                        // the gaps are written by the first launch
-    }
-    return hipSuccess;
+        a.zero_groups = 0;                                               // the gaps are written by the first launch
+        return hipGetLastError();
+    });
 }
 
-template <int CAP>
-static hipError_t dft_alloc_prepare_cap() {
-    return load_kernels(dft_alloc_rows_kernel<CAP>, despread_alloc_rows_kernel<2, false, CAP>, despread_alloc_rows_kernel<2, true, CAP>,
-                        despread_alloc_rows_kernel<4, true, CAP>, despread_alloc_rows_kernel<6, true, CAP>);
-}
 hipError_t dft_alloc_prepare() {
-    hipError_t e = load_kernels(despread_alloc_table_kernel);
-    if (e == hipSuccess) e = dft_alloc_prepare_cap<DFT_SMALL_M>();
-    if (e == hipSuccess) e = dft_alloc_prepare_cap<DFT_MAX_M>();
-    return e;
+    const hipError_t e = load_kernels(despread_alloc_table_kernel, dft_alloc_rows_kernel<DFT_SMALL_M>, dft_alloc_rows_kernel<DFT_MAX_M>);
+    if (e != hipSuccess) return e;
+    return each_row_instance([](auto I) { return load_kernels(despread_alloc_rows_kernel<I.mod, I.more, I.cap>); });
 }
 
 }  // namespace ofdm

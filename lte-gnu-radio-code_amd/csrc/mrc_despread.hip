@@ -18,42 +18,14 @@
 // CAP: compiled for M <= DFT_SMALL_M and for every M (dft_mixed.hpp, DftLaneWork).  Every float32 product, sum and quotient is
 // rounded on its own (contraction off).
 #include "dft_rows_device.hpp"
-#include "demap_hard.hpp"
+#include "dft_rows_launch.hpp"
 
 namespace ofdm {
 
-namespace {
-
-// Steps 2 and 3 of the combiner for one branch, as mrc_add of rx_mrc.hip (that file's kernels keep their own copy, see there):
-// t = {c, t} of the entry (c = 0: not usable).  Returns whether the branch takes part; one that does not leaves the sums.
-struct CombAcc {
-    float nr, ni, a;
-};
-__device__ __forceinline__ bool comb_add(CombAcc& s, cf z, float2 t) {
-#pragma clang fp contract(off)
-    const float pr = z.x * t.x, pi = z.y * t.x;
-    const bool in = t.x != 0.f && soft_finite(z.x) && soft_finite(z.y) && (z.x != 0.f || z.y != 0.f) && soft_finite(pr) && soft_finite(pi);
-    const float nr = s.nr + pr, ni = s.ni + pi, a = s.a + t.y;
-    s.nr = in ? nr : s.nr;
-    s.ni = in ? ni : s.ni;
-    s.a = in ? a : s.a;
-    return in;
-}
-// Step 4: v = N / (A + 1).  `took` comes back as 0 where the symbol is not combined (then v = 0 and A counts as 0).
-__device__ __forceinline__ cf comb_finish(CombAcc s, unsigned& took) {
-#pragma clang fp contract(off)
-    const float den = s.a + 1.0f;
-    const float vr = s.nr / den, vi = s.ni / den;
-    const bool ok = took != 0u && soft_finite(s.a) && s.a > 0.f && soft_finite(vr) && soft_finite(vi);
-    took = ok ? took : 0u;
-    return ok ? cf{vr, vi} : cf{0.f, 0.f};
-}
-
-// Branches whose loads a lane issues before any arithmetic: MRC_ROUND of rx_mrc.hip and its reasons.
-constexpr int COMB_ROUND = 2;
-
-}  // namespace
-
+// This kernel keeps the stages as text of its own.  Through combine_row, row_weights and despread_epilogue_rows (dft_rows_device.hpp),
+// which mrc_despread_alloc_rows_kernel calls, it measured 1.3 ... 1.9 % slower where the spread of the timed calls was 0.8 ... 1.5 %
+// (DESIGN.md 9.2.19); comb_add, comb_finish and COMB_ROUND are the header's.  A change to a stage here is a change to its function
+// there: the block-equality tests of test_gpu_mrc_despread_alloc.py compare the two on every output.
 template <int MOD, bool MORE, int CAP>
 __global__ void __launch_bounds__(DFT_THREADS) mrc_despread_rows_kernel(MrcDespreadArgs a) {
 #pragma clang fp contract(off)
@@ -258,37 +230,20 @@ __global__ void __launch_bounds__(DFT_THREADS) mrc_despread_rows_kernel(MrcDespr
     }
 }
 
-template <int CAP>
-static hipError_t launch_mrc_despread_cap(const MrcDespreadArgs& a, hipStream_t s) {
-    const dim3 g(unsigned(a.n_seg * a.groups_per_seg)), b(DFT_THREADS);
-    if (!a.llr && !a.bits) {
-        hipLaunchKernelGGL((mrc_despread_rows_kernel<2, false, CAP>), g, b, 0, s, a);
-    } else {
-        switch (a.mod) {
-            case 2: hipLaunchKernelGGL((mrc_despread_rows_kernel<2, true, CAP>), g, b, 0, s, a); break;
-            case 4: hipLaunchKernelGGL((mrc_despread_rows_kernel<4, true, CAP>), g, b, 0, s, a); break;
-            case 6: hipLaunchKernelGGL((mrc_despread_rows_kernel<6, true, CAP>), g, b, 0, s, a); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
-}
 // The caller has checked the arguments (n_seg * groups_per_seg fits the grid, packed bits fill a row's bytes) and run the table.
 hipError_t launch_mrc_despread(const MrcDespreadArgs& a, hipStream_t s) {
     if (a.n_seg <= 0 || a.rows <= 0) return hipSuccess;
-    return a.pl.M <= DFT_SMALL_M ? launch_mrc_despread_cap<DFT_SMALL_M>(a, s) : launch_mrc_despread_cap<DFT_MAX_M>(a, s);
+    const dim3 g(unsigned(a.n_seg * a.groups_per_seg)), b(DFT_THREADS);
+    return with_row_instance(a.pl.M <= DFT_SMALL_M, a.llr || a.bits, a.mod, [&](auto I) {
+        hipLaunchKernelGGL((mrc_despread_rows_kernel<I.mod, I.more, I.cap>), g, b, 0, s, a);
+        return hipGetLastError();
+    });
 }
 
-template <int CAP>
-static hipError_t mrc_despread_prepare_cap() {
-    return load_kernels(mrc_despread_rows_kernel<2, false, CAP>, mrc_despread_rows_kernel<2, true, CAP>,
-                        mrc_despread_rows_kernel<4, true, CAP>, mrc_despread_rows_kernel<6, true, CAP>);
-}
 hipError_t mrc_despread_prepare() {
-    hipError_t e = mrc_table_prepare();
-    if (e == hipSuccess) e = mrc_despread_prepare_cap<DFT_SMALL_M>();
-    if (e == hipSuccess) e = mrc_despread_prepare_cap<DFT_MAX_M>();
-    return e;
+    const hipError_t e = mrc_table_prepare();
+    if (e != hipSuccess) return e;
+    return each_row_instance([](auto I) { return load_kernels(mrc_despread_rows_kernel<I.mod, I.more, I.cap>); });
 }
 
 }  // namespace ofdm
