@@ -31,9 +31,8 @@ const char* csi_bad_reserve(int64_t n_seg, int64_t rows, int64_t row_len) {
 }
 // grows the workspace; refuses inside a stream capture (growing synchronises and allocates)
 int csi_ensure(ofdm_rx* h, int64_t n_seg, int64_t rows, int64_t row_len, hipStream_t s, const char* who) {
-    if (n_seg * seg_slices(rows * row_len) <= h->cap_csi_items && n_seg * row_len <= h->cap_csi_tab) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_csi");
-    return rc != OFDM_OK ? rc : ofdm_rx_reserve_csi(h, n_seg, rows, row_len);
+    return grow_outside_capture(n_seg * seg_slices(rows * row_len) <= h->cap_csi_items && n_seg * row_len <= h->cap_csi_tab, s, who,
+                                "ofdm_rx_reserve_csi", [&] { return ofdm_rx_reserve_csi(h, n_seg, rows, row_len); });
 }
 int csi_launch(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, const float* d_csi,
                int64_t csi_stride, float rho, int32_t modulation, int32_t noise_mode, double noise_var, const ofdm_csi_out* out,

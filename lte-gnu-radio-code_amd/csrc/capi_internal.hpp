@@ -283,14 +283,18 @@ struct ofdm_tx {
     DftAllocSet alloc{};                 // ofdm_tx_set_allocations
 };
 
-// capi_dft.hip: frees the tables of a handle's plans (the destroys)
+// capi_dft.hip: frees the tables of a handle's plans (the destroys); what else the DFT-spread units share is in capi_dft.hpp
 #pragma GCC visibility push(hidden)
 void dft_plans_free(DftPlanCache& c);
 void dft_alloc_free(DftAllocSet& a);     // capi_dft.hip: frees a handle's allocation set (the destroys)
-// capi_mrc.hip: what ofdm_combine_csi_frames checks about its arguments alone; "" = fine
+// capi_mrc.hip, shared with the combining stages of capi_despread.hip: the branch count and what ofdm_combine_csi_frames checks
+// about its arguments alone ("" = fine), and the arguments of the combiner's {c, t} table
+const char* mrc_bad_branches(int32_t n_branch);
 const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
                          float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
                          bool composite);
+MrcArgs mrc_table_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, const float* d_csi,
+                       int64_t csi_stride, float rho, int32_t modulation, const double* h_noise_var, const double* d_sigma2, float2* tab);
 #pragma GCC visibility pop
 
 namespace {
@@ -385,6 +389,13 @@ int refuse_growth_in_capture(hipStream_t s, const char* who, const char* reserve
     if (stream_is_capturing(s))
         return fail(OFDM_ERR_INVALID, "%s: workspace must grow, which cannot happen inside a capture (call %s first)", who, reserve_name);
     return OFDM_OK;
+}
+// the tail of every ensure step: the workspace fits, or it grows through `reserve` (the call named reserve_name) -- outside a capture
+template <class Reserve>
+int grow_outside_capture(bool fits, hipStream_t s, const char* who, const char* reserve_name, Reserve reserve) {
+    if (fits) return OFDM_OK;
+    const int rc = refuse_growth_in_capture(s, who, reserve_name);
+    return rc != OFDM_OK ? rc : reserve();
 }
 
 // input buffer of a stream block: grown with a quarter of headroom, after the work queued on `s` has drained
@@ -517,13 +528,6 @@ int prepare_only(H* h, const char* who, hipError_t (*prepare)()) {
     HIP_TRY(hipSetDevice(h->cfg.device));
     HIP_TRY(prepare());
     return OFDM_OK;
-}
-// the ensure step of both turbo decoders: the handle's workspace holds `need` floats, or grows through `reserve` -- outside a capture
-int turbo_ensure(ofdm_rx* h, int64_t need, int64_t n_blocks, int32_t K, hipStream_t s, const char* who, const char* reserve_name,
-                 int (*reserve)(ofdm_rx*, int64_t, int32_t)) {
-    if (need <= h->cap_turbo) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, who, reserve_name);
-    return rc != OFDM_OK ? rc : reserve(h, n_blocks, K);
 }
 
 }  // namespace

@@ -8,15 +8,18 @@ namespace {
 static_assert(OFDM_MRC_MAX_BRANCHES == MRC_MAX_BRANCHES, "the header's branch limit is the kernels'");
 bool mrc_wanted(const ofdm_mrc_out* o) { return o && (o->llr || o->sym || o->weight); }
 bool mrc_units_ok(int32_t n_branch, int64_t n_seg) { return n_seg <= SOFT_MAX_N / n_branch; }
+constexpr const char* BAD_BRANCHES = "n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES";
 }  // namespace
 
+// Declared in capi_internal.hpp: the stages of capi_despread.hip that combine branches make the same checks and fill the same table.
+const char* mrc_bad_branches(int32_t n_branch) { return n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES ? BAD_BRANCHES : ""; }
 // what the arguments alone decide (no read of the handle, no device access); "" = fine.  composite: the call that takes
-// the variances from the host or estimates them.  Declared in capi_internal.hpp: capi_dft.hip makes the same checks.
+// the variances from the host or estimates them.
 const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, int64_t csi_stride,
                          float rho, int32_t modulation, int32_t noise_mode, const double* h_noise_var, const double* d_sigma2,
                          bool composite) {
     if (n_seg < 0 || rows < 0 || row_len < 0) return "negative count";
-    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES) return "n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES";
+    if (*mrc_bad_branches(n_branch)) return mrc_bad_branches(n_branch);
     if (row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len)) return "index range exceeded (rows * row_len)";
     if (seg_stride < rows * row_len) return "seg_stride < rows * row_len";
     if (csi_stride < row_len) return "csi_stride < row_len";
@@ -40,6 +43,25 @@ const char* mrc_bad_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t 
         return "index range exceeded (batch beyond the kernels' index range)";
     return "";
 }
+// the arguments of the combiner's {c, t} table; d_sigma2 == null: the host array (OFDM_MRC_NOISE_GIVEN)
+MrcArgs mrc_table_args(int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride, const float* d_csi,
+                       int64_t csi_stride, float rho, int32_t modulation, const double* h_noise_var, const double* d_sigma2, float2* tab) {
+    MrcArgs a{};
+    a.n_branch = n_branch;
+    a.n_seg = n_seg;
+    a.rows = rows;
+    a.seg_stride = seg_stride;
+    a.row_len = int(row_len);
+    a.seg_len = rows * row_len;
+    a.csi = d_csi;
+    a.csi_stride = csi_stride;
+    a.rho = rho;
+    a.mod = modulation;
+    a.sigma2 = d_sigma2;
+    for (int b = 0; b < MRC_MAX_BRANCHES; ++b) a.noise_var[b] = (!d_sigma2 && b < n_branch) ? h_noise_var[b] : 0.0;
+    a.tab = tab;
+    return a;
+}
 
 namespace {
 // grows the workspace; refuses inside a stream capture (growing synchronises and allocates)
@@ -50,33 +72,18 @@ int mrc_ensure(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t rows, int64_
     if (composite)
         fits = fits && units <= h->cap_mrc_units && units * seg_slices(rows * row_len) <= h->cap_csi_items &&
                units * row_len <= h->cap_csi_tab;
-    if (fits) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_mrc");
-    return rc != OFDM_OK ? rc : ofdm_rx_reserve_mrc(h, n_branch, n_seg, rows, row_len);
+    return grow_outside_capture(fits, s, who, "ofdm_rx_reserve_mrc", [&] { return ofdm_rx_reserve_mrc(h, n_branch, n_seg, rows, row_len); });
 }
 int mrc_launch(ofdm_rx* h, const float* d_sym, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len, int64_t seg_stride,
                const float* d_csi, int64_t csi_stride, float rho, int32_t modulation, const double* h_noise_var,
                const double* d_sigma2, const ofdm_mrc_out* out, double* d_sigma2_out, hipStream_t s) {
-    MrcArgs a{};
+    MrcArgs a = mrc_table_args(n_branch, n_seg, rows, row_len, seg_stride, d_csi, csi_stride, rho, modulation, h_noise_var, d_sigma2, h->m_tab);
     a.sym = reinterpret_cast<const cf*>(d_sym);
-    a.n_branch = n_branch;
-    a.n_seg = n_seg;
-    a.rows = rows;
-    a.seg_stride = seg_stride;
-    a.row_len = int(row_len);
-    a.seg_len = rows * row_len;
     a.n_slices = seg_slices(a.seg_len);
-    a.csi = d_csi;
-    a.csi_stride = csi_stride;
-    a.rho = rho;
-    a.mod = modulation;
-    a.sigma2 = d_sigma2;
-    for (int b = 0; b < MRC_MAX_BRANCHES; ++b) a.noise_var[b] = (!d_sigma2 && b < n_branch) ? h_noise_var[b] : 0.0;
     a.llr = out ? out->llr : nullptr;
     a.osym = out ? reinterpret_cast<cf*>(out->sym) : nullptr;
     a.weight = out ? out->weight : nullptr;
     a.sigma2_out = d_sigma2_out;
-    a.tab = h->m_tab;
     HIP_TRY(launch_combine_mrc(a, s));
     return OFDM_OK;
 }
@@ -87,8 +94,7 @@ extern "C" {
 int ofdm_rx_reserve_mrc(ofdm_rx* h, int32_t n_branch, int64_t n_seg, int64_t rows, int64_t row_len) {
     if (!h) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: null handle");
     if (n_seg < 0 || rows < 0 || row_len < 0) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: negative count");
-    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES)
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES");
+    if (*mrc_bad_branches(n_branch)) return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: %s", mrc_bad_branches(n_branch));
     if (!mrc_units_ok(n_branch, n_seg) || row_len > SOFT_MAX_ROW || (row_len > 0 && rows > SOFT_MAX_LEN / row_len) ||
         (n_seg > 0 && row_len > SOFT_MAX_LEN / (n_branch * n_seg)))
         return fail(OFDM_ERR_INVALID, "ofdm_rx_reserve_mrc: batch too large");
@@ -126,8 +132,8 @@ int64_t ofdm_rx_demod_frames_mrc(ofdm_rx* h, const float* d_iq, int32_t n_branch
                                  const ofdm_mrc_out* out, double* d_sigma2_out, void* stream) {
     const int open = demod_stage_open(h, d_iq != nullptr, n_frames, frame_stride, frame_len, "ofdm_rx_demod_frames_mrc");
     if (open != OFDM_OK) return open;
-    if (n_branch < 1 || n_branch > OFDM_MRC_MAX_BRANCHES || !mrc_units_ok(n_branch, n_frames))
-        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: n_branch must lie in 1 .. OFDM_MRC_MAX_BRANCHES");
+    if (*mrc_bad_branches(n_branch) || !mrc_units_ok(n_branch, n_frames))
+        return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: %s", BAD_BRANCHES);
     if (!d_eq) return fail(OFDM_ERR_INVALID, "ofdm_rx_demod_frames_mrc: the combiner needs d_eq (it reads it)");
     const RxDev& d = h->dev;
     const int mod = h->cfg.modulation;

@@ -15,9 +15,8 @@ const char* soft_bad_args(int64_t n_seg, int64_t seg_len, int64_t seg_stride) {
 }
 // grows the partial-sum workspace; refuses inside a stream capture (growing synchronises and allocates)
 int soft_ensure(ofdm_rx* h, int64_t n_seg, int64_t seg_len, hipStream_t s, const char* who) {
-    if (n_seg * seg_slices(seg_len) <= h->cap_seg_partial) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_soft");
-    return rc != OFDM_OK ? rc : ofdm_rx_reserve_soft(h, n_seg, seg_len);
+    return grow_outside_capture(n_seg * seg_slices(seg_len) <= h->cap_seg_partial, s, who, "ofdm_rx_reserve_soft",
+                                [&] { return ofdm_rx_reserve_soft(h, n_seg, seg_len); });
 }
 int soft_launch(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t seg_len, int64_t seg_stride, int32_t modulation,
                 const ofdm_soft_out* out, hipStream_t s) {
@@ -126,9 +125,7 @@ const char* pilot_bad_args(const ofdm_rx* h, int64_t n_seg, int64_t rows, int64_
 }
 // grows the pilot-sum workspace; refuses inside a stream capture (growing synchronises and allocates)
 int pilot_ensure(ofdm_rx* h, int64_t n_seg, int64_t rows, hipStream_t s, const char* who) {
-    if (n_seg * rows <= h->cap_usum) return OFDM_OK;
-    const int rc = refuse_growth_in_capture(s, who, "ofdm_rx_reserve_pilots");
-    return rc != OFDM_OK ? rc : ofdm_rx_reserve_pilots(h, n_seg, rows);
+    return grow_outside_capture(n_seg * rows <= h->cap_usum, s, who, "ofdm_rx_reserve_pilots", [&] { return ofdm_rx_reserve_pilots(h, n_seg, rows); });
 }
 int pilot_launch(ofdm_rx* h, const float* d_sym, int64_t n_seg, int64_t rows, int64_t seg_stride, int32_t rows_per_pattern,
                  int32_t mode, const ofdm_pilot_out* out, hipStream_t s) {

@@ -97,8 +97,8 @@ int ofdm_turbo_decode_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, int6
     hipStream_t s = pick_stream(h, stream);
     const int64_t n_blocks = n_seg * blocks_per_seg;
     HIP_TRY(hipSetDevice(h->cfg.device));
-    const int rc = turbo_ensure(h, turbo_ws_floats(n_blocks, K), n_blocks, K, s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo",
-                                ofdm_rx_reserve_turbo);
+    const int rc = grow_outside_capture(turbo_ws_floats(n_blocks, K) <= h->cap_turbo, s, "ofdm_turbo_decode_frames", "ofdm_rx_reserve_turbo",
+                                        [&] { return ofdm_rx_reserve_turbo(h, n_blocks, K); });
     if (rc != OFDM_OK) return rc;
     TurboDecArgs a{};
     dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, out);
@@ -139,8 +139,8 @@ int ofdm_turbo_decode_es_frames(ofdm_rx* h, const float* d_llr, int64_t n_seg, i
     hipStream_t s = pick_stream(h, stream);
     const int64_t n_blocks = n_seg * blocks_per_seg;
     HIP_TRY(hipSetDevice(h->cfg.device));
-    const int rc = turbo_ensure(h, turbo_es_ws_floats(n_blocks, K), n_blocks, K, s, "ofdm_turbo_decode_es_frames",
-                                "ofdm_rx_reserve_turbo_es", ofdm_rx_reserve_turbo_es);
+    const int rc = grow_outside_capture(turbo_es_ws_floats(n_blocks, K) <= h->cap_turbo, s, "ofdm_turbo_decode_es_frames",
+                                        "ofdm_rx_reserve_turbo_es", [&] { return ofdm_rx_reserve_turbo_es(h, n_blocks, K); });
     if (rc != OFDM_OK) return rc;
     TurboDecEsArgs a{};
     dec_fill(a, d_llr, n_seg, seg_stride, blocks_per_seg, out);

@@ -481,12 +481,17 @@ class RxEngine(_Handle):
         return _lib.MrcOut(_addr(d_llr), _addr(d_sym_out), _addr(d_weight))
 
     @staticmethod
-    def _mrc_noise(noise_var, n_branch):
-        """the host array of OFDM_MRC_NOISE_GIVEN: n_branch doubles"""
+    def _mrc_noise(who, n_branch, noise_var, d_sigma2=None, other=MRC_NOISE_SEG):
+        """(noise_mode, host array) of the combiners: OFDM_MRC_NOISE_GIVEN with the n_branch doubles of noise_var, or `other` with
+        None.  who: the method whose caller gives exactly one of noise_var and d_sigma2 (None: noise_var alone decides)."""
+        if who and (noise_var is None) == (d_sigma2 is None):
+            raise ValueError("%s: give exactly one of noise_var and d_sigma2" % who)
+        if noise_var is None:
+            return other, None
         nv = [float(v) for v in noise_var]
         if len(nv) != int(n_branch):
             raise ValueError("noise_var must hold n_branch = %d numbers, got %d" % (int(n_branch), len(nv)))
-        return (C.c_double * len(nv))(*nv)
+        return MRC_NOISE_GIVEN, (C.c_double * len(nv))(*nv)
 
     def reserve_mrc(self, n_branch: int, n_seg: int, rows: int, row_len: int):
         """Workspace of combine_csi_frames / demod_frames_mrc for n_branch branches of n_seg segments of `rows` rows of row_len
@@ -499,14 +504,11 @@ class RxEngine(_Handle):
         d_sym + g*seg_stride with the channel powers d_csi[g*csi_stride + j].  Exactly one of noise_var (n_branch numbers, one
         variance per branch) and d_sigma2 (device, [n_branch*n_seg] float64, one per unit) is given.  Outputs per segment: llr
         [rows*row_len*bps] float32 (positive favours bit 0), sym [rows*row_len] complex64, weight [rows*row_len] float32."""
-        if (noise_var is None) == (d_sigma2 is None):
-            raise ValueError("combine_csi_frames: give exactly one of noise_var and d_sigma2")
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise("combine_csi_frames", n_branch, noise_var, d_sigma2)
         out = self._mrc_out(d_llr, d_sym_out, d_weight)
         check(self.lib.ofdm_combine_csi_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(row_len),
                                                int(seg_stride), ptr(d_csi), int(csi_stride), float(rho), _mod_bits(modulation),
-                                               MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2), C.byref(out),
+                                               mode, nv, ptr(d_sigma2), C.byref(out),
                                                ptr(stream)))
 
     def demod_frames_mrc(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_llr=None, d_sym_out=None,
@@ -515,12 +517,11 @@ class RxEngine(_Handle):
         csi_frames(CSI_ROWS_ALL) and combine_csi_frames over d_eq with one segment per frame (n_dsym rows of Kd symbols, the
         handle's rho and modulation).  noise_var: n_branch numbers, or None for the per-frame estimate of demod_frames_csi.
         d_sigma2 [n_branch*n_frames] float64 receives the variances used.  Returns n_dsym."""
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise(None, n_branch, noise_var, other=MRC_NOISE_EST)
         out = self._mrc_out(d_llr, d_sym_out, d_weight)
         return int(check(self.lib.ofdm_rx_demod_frames_mrc(self._h, ptr(d_iq), int(n_branch), int(n_frames), int(frame_stride),
                                                            int(frame_len), ptr(d_eq), ptr(d_tsr),
-                                                           MRC_NOISE_GIVEN if given else MRC_NOISE_EST, nv, C.byref(out),
+                                                           mode, nv, C.byref(out),
                                                            ptr(d_sigma2), ptr(stream))))
 
     # ---- receive diversity for DFT-spread OFDM: B branches combined per bin, then despread (include/ofdm_mi355x.h) ---------------
@@ -541,14 +542,11 @@ class RxEngine(_Handle):
         numbers, one variance per branch) and d_sigma2 (device, [n_branch*n_seg] float64, one per unit) is given; their absolute
         level matters.  Outputs per segment: sym [rows*M] complex64, llr [rows*M*bps] float32 (positive favours bit 0), hard
         bits, beta and weight [rows] float32 (one per ROW), comb [rows*M] complex64 (the combined symbols before the transform)."""
-        if (noise_var is None) == (d_sigma2 is None):
-            raise ValueError("combine_despread_frames: give exactly one of noise_var and d_sigma2")
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise("combine_despread_frames", n_branch, noise_var, d_sigma2)
         out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
         check(self.lib.ofdm_combine_despread_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(M),
                                                     int(seg_stride), ptr(d_csi), int(csi_stride), float(rho), _mod_bits(modulation),
-                                                    MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2), int(bits_mode),
+                                                    mode, nv, ptr(d_sigma2), int(bits_mode),
                                                     C.byref(out), ptr(stream)))
 
     def demod_frames_mrc_despread(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_sigma2=None,
@@ -558,14 +556,11 @@ class RxEngine(_Handle):
         csi_frames(CSI_ROWS_ALL) into the workspace and combine_despread_frames over d_eq with one segment per frame (n_dsym rows
         of M = Kd symbols, the handle's rho and modulation).  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device,
         [n_branch*n_frames] float64).  Returns n_dsym."""
-        if (noise_var is None) == (d_sigma2 is None):
-            raise ValueError("demod_frames_mrc_despread: give exactly one of noise_var and d_sigma2")
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise("demod_frames_mrc_despread", n_branch, noise_var, d_sigma2)
         out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
         return int(check(self.lib.ofdm_rx_demod_frames_mrc_despread(self._h, ptr(d_iq), int(n_branch), int(n_frames),
                                                                     int(frame_stride), int(frame_len), ptr(d_eq), ptr(d_tsr),
-                                                                    MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2),
+                                                                    mode, nv, ptr(d_sigma2),
                                                                     int(bits_mode), C.byref(out), ptr(stream))))
 
     # ---- receive diversity for multi-user allocations of DFT-spread OFDM (include/ofdm_mi355x.h) ---------------------------------
@@ -582,14 +577,11 @@ class RxEngine(_Handle):
         d_csi[g*csi_stride + k].  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device, [n_branch*n_seg] float64).
         sym, comb, llr and bits are allocation-major and dense (alloc_layout; comb at the sym offsets); beta and weight are
         [n_alloc][n_seg][rows]."""
-        if (noise_var is None) == (d_sigma2 is None):
-            raise ValueError("combine_despread_alloc_frames: give exactly one of noise_var and d_sigma2")
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise("combine_despread_alloc_frames", n_branch, noise_var, d_sigma2)
         out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
         check(self.lib.ofdm_combine_despread_alloc_frames(self._h, ptr(d_sym), int(n_branch), int(n_seg), int(rows), int(row_len),
                                                           int(seg_stride), ptr(d_csi), int(csi_stride), float(rho),
-                                                          MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv, ptr(d_sigma2),
+                                                          mode, nv, ptr(d_sigma2),
                                                           int(bits_mode), C.byref(out), ptr(stream)))
 
     def demod_frames_mrc_despread_alloc(self, d_iq, n_branch, n_frames, frame_stride, frame_len, d_eq, noise_var=None, d_sigma2=None,
@@ -599,14 +591,11 @@ class RxEngine(_Handle):
         csi_frames(CSI_ROWS_ALL) into the workspace and combine_despread_alloc_frames over d_eq with one segment per frame (n_dsym
         rows of row_len = Kd symbols, the handle's rho).  Exactly one of noise_var (n_branch numbers) and d_sigma2 (device,
         [n_branch*n_frames] float64).  Returns n_dsym."""
-        if (noise_var is None) == (d_sigma2 is None):
-            raise ValueError("demod_frames_mrc_despread_alloc: give exactly one of noise_var and d_sigma2")
-        given = noise_var is not None
-        nv = self._mrc_noise(noise_var, n_branch) if given else None
+        mode, nv = self._mrc_noise("demod_frames_mrc_despread_alloc", n_branch, noise_var, d_sigma2)
         out = self._mrc_despread_out(d_sym_out, d_llr, d_bits, d_beta, d_weight, d_comb)
         return int(check(self.lib.ofdm_rx_demod_frames_mrc_despread_alloc(self._h, ptr(d_iq), int(n_branch), int(n_frames),
                                                                           int(frame_stride), int(frame_len), ptr(d_eq), ptr(d_tsr),
-                                                                          MRC_NOISE_GIVEN if given else MRC_NOISE_SEG, nv,
+                                                                          mode, nv,
                                                                           ptr(d_sigma2), int(bits_mode), C.byref(out), ptr(stream))))
 
     # ---- delay-window denoising of the LS channel estimate (include/ofdm_mi355x.h) ----------------------------------------------

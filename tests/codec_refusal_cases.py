@@ -556,6 +556,7 @@ assert len(set(IDS)) == len(IDS), sorted(i for i in IDS if IDS.count(i) > 1)
 
 class Runner:
     """makes the table's calls on one transmitter and one receiver handle of library `om` (ofdm_mi355x, loaded)"""
+    calls, out_types = CALLS, OUT_TYPES                      # the table: tests/despread_refusal_cases.py runs its own
 
     def __init__(self, om):
         from ofdm_mi355x import _lib
@@ -572,7 +573,7 @@ class Runner:
         if name == "out":
             if v is None:
                 return None
-            s = getattr(self._lib, OUT_TYPES[call])()
+            s = getattr(self._lib, self.out_types[call])()
             for k, x in v.items():
                 setattr(s, k, self.buf.data_ptr() if x == "BUF" else x)
             self.keep.append(s)
@@ -588,7 +589,7 @@ class Runner:
         return v
 
     def run(self, call, kwargs):
-        args = [self.value(call, n, kwargs[n]) for n in CALLS[call]]
+        args = [self.value(call, n, kwargs[n]) for n in self.calls[call]]
         status = int(getattr(self.lib, call)(*args))
         self.keep.clear()
         return [status, self.lib.ofdm_last_error().decode() if status < 0 else ""]
